@@ -24,10 +24,15 @@ GPUs); weak: every rank owns nex x ney elements.
 
 Rank 0 prints ONE JSON line (the driver's contract) with a ``roofline``
 object for the element kernel (algorithmic bytes of SURVEY.md §8(d) / HIP
-event time on the launch stream), a ``parity`` spot check of the timed
-output against the NumPy oracle, and, at N = 1, a ``cpu_baseline`` object
-(the oracle of the reference path timed on this host's cores on bounded
-samples, in a child process with OMP_NUM_THREADS pinned).
+event time on the launch stream).  A plain run sets up, warms up, times the
+K steps and prints that line; with --dump-outputs DIR it also writes the
+output of the last timed step to DIR/<name>.npy (dump_outputs).
+
+--full adds what takes runs of its own: a ``parity`` spot check of the timed
+output against the NumPy oracle, at N = 1 a ``cpu_baseline`` object (the
+oracle of the reference path timed on this host's cores on bounded samples,
+in a child process with OMP_NUM_THREADS pinned), and the per-action kernel
+time min / quartiles / max from a second, untimed pass of K actions.
 """
 import argparse
 import json
@@ -59,6 +64,28 @@ JSON_OUT = sys.stdout  # the driver's JSON line (rank 0)
 
 def log(msg):
     print("[bench] " + msg, file=sys.stderr, flush=True)
+
+
+DUMP_MAX_VALUES = 1 << 22  # float64 values per run (32 MiB) over all ranks
+
+
+def dump_outputs(dirname, name, t, rank=0, world=1):
+    """--dump-outputs: the vector the timed path returned in its last step as
+    DIR/<name>.npy (float64; with several ranks each rank's own vector as
+    DIR/<name>_rank<r>.npy).  A vector longer than the rank's share of
+    DUMP_MAX_VALUES is written as a fixed sample: its entries at the sorted
+    indices drawn from default_rng(0), the same in every run with the same
+    arguments (the inputs are seeded too, so two builds compare entry for
+    entry)."""
+    os.makedirs(dirname, exist_ok=True)
+    t = t.reshape(-1)
+    cap = DUMP_MAX_VALUES // world
+    if t.numel() > cap:
+        idx = np.sort(np.random.default_rng(0).integers(0, t.numel(), cap))
+        t = t[torch_index(idx, t.device)]
+    path = os.path.join(dirname, name + ("_rank%d" % rank if world > 1 else "") + ".npy")
+    np.save(path, t.cpu().numpy().astype(np.float64, copy=False))
+    log("rank %d: wrote %d values to %s" % (rank, t.numel(), path))
 
 
 # ---------------------------------------------------------------- byte models
@@ -491,11 +518,13 @@ def bench_hex(args):
     if world > 1:
         dist.barrier()
     elapsed = time.perf_counter() - t_start
-    if not each:  # untimed: per-action quartiles
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, "y", y, rank, world)
+    if not each and args.full:  # untimed: per-action quartiles
         for k in range(args.steps):
             op.step(u, y, events[k])
         torch.cuda.synchronize()
-    kern_ms = [a.elapsed_time(b) for a, b in events]
+    kern_ms = [a.elapsed_time(b) for a, b in events] if each or args.full else None
     kern_avg_s = (float(np.mean(kern_ms)) if each else
                   region[0].elapsed_time(region[1]) / args.steps) / 1e3
     per_rank_ms = [elapsed / args.steps * 1e3]
@@ -507,7 +536,7 @@ def bench_hex(args):
         dist.all_gather_object(gathered, per_rank_ms[0])
         per_rank_ms = gathered
     parity, parity_iface, parity_ranks = None, None, None
-    if not args.no_check:
+    if args.full and not args.no_check:
         parity, parity_iface = hex_parity_checks(op, y, u, part, p, args.warp, dev, world)
         log("rank %d: hex parity %s; interface %s" % (rank, parity, parity_iface))
         assert parity["rel_l2"] < parity["tolerance"], parity
@@ -553,12 +582,14 @@ def bench_hex(args):
             "per_rank_ms_per_step": per_rank_ms,
             "exchange_bytes_per_step_per_rank": 2 * op.exchange_bytes,
             "interface_elements": op.n_iface_elem,
-            "kernel_ms_avg": kern_avg_s * 1e3, "kernel_ms_min": float(np.min(kern_ms)),
-            "kernel_ms_quartiles": [float(q) for q in np.percentile(kern_ms, [25, 50, 75])],
+            "kernel_ms_avg": kern_avg_s * 1e3,
+            "kernel_ms_min": float(np.min(kern_ms)) if kern_ms else None,
+            "kernel_ms_quartiles": [float(q) for q in np.percentile(kern_ms, [25, 50, 75])]
+            if kern_ms else None,
             "kernel_ms_note": ("HIP events around each step on the launch stream" if each else
                                "HIP events around the K timed steps / K (element kernel + seam "
                                "sum + the gaps); min / quartiles from per-step events of a "
-                               "second, untimed pass"),
+                               "second, untimed pass (--full)"),
             "step_events": args.step_events,
             "decomposition": op.dd_info(),
             "gflops_kernel": F / kern_avg_s / 1e9, "gpu_setup_sec": t_setup,
@@ -579,7 +610,7 @@ def bench_hex(args):
     if parity_iface is not None or parity_ranks is not None:
         result["parity_interface"] = parity_iface
         result["parity_per_rank"] = parity_ranks
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         log("timing CPU baseline (hexahedral NumPy oracle, child process)...")
         env = dict(os.environ, OMP_NUM_THREADS="1", OPENBLAS_NUM_THREADS="1",
                    MKL_NUM_THREADS="1")
@@ -821,9 +852,17 @@ def main():
                          "then from an untimed pass), or a pair around every timed action")
     ap.add_argument("--kernel-series", action="store_true",
                     help="also write every timed action's HIP-event time into the JSON")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the parity checks "
+                         "against the oracle, the CPU baseline (one GPU) and the second, untimed "
+                         "pass for the per-action kernel time quartiles")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the output of the last timed step to DIR/<name>.npy (float64; "
+                         "above %d values a fixed, seeded sample)" % DUMP_MAX_VALUES)
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="--full without the CPU baseline")
     ap.add_argument("--no-check", action="store_true",
-                    help="skip the parity spot check (timing-only diagnostic builds)")
+                    help="--full without the parity checks (timing-only diagnostic builds)")
     ap.add_argument("--cpu-budget", type=float, default=20.0)
     ap.add_argument("--cpu-workers", type=int, default=16)
     ap.add_argument("--cpu-baseline-only", action="store_true", help=argparse.SUPPRESS)
@@ -869,6 +908,8 @@ def main():
         print(json.dumps(fn(args.p, args.warp, args.cpu_budget, args.cpu_workers)))
         return 0
     if args.time_rank is not None:
+        if args.dump_outputs:
+            raise SystemExit("--dump-outputs: the values of --time-rank are not the action")
         return time_rank(args)
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         return launch_ranks(args.gpus, args.deadline)
@@ -985,13 +1026,17 @@ def main():
     if world > 1:
         dist.barrier()
     elapsed = time.perf_counter() - t_start
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, "y", y, rank, world)
     region_ms = None
     if args.step_events == "region":
         region_ms = region[0].elapsed_time(region[1]) / args.steps
-        for k in range(args.steps):  # untimed: per-action quartiles
-            op.step(u, y, events[k])
-        torch.cuda.synchronize()
-    kern_ms = [a.elapsed_time(b) for a, b in events]
+        if args.full:
+            for k in range(args.steps):  # untimed: per-action quartiles
+                op.step(u, y, events[k])
+            torch.cuda.synchronize()
+    kern_ms = ([a.elapsed_time(b) for a, b in events]
+               if args.full or region_ms is None else None)
     per_rank_ms = [elapsed / args.steps * 1e3]
     if world > 1:
         t = torch.tensor([elapsed], dtype=torch.float64)
@@ -1003,7 +1048,8 @@ def main():
     kern_avg_s = (region_ms if region_ms is not None else float(np.mean(kern_ms))) / 1e3
 
     parity, parity_ranks, parity_iface = None, None, None
-    if not args.no_check and args.numbering == "rcm":
+    check = args.full and not args.no_check
+    if check and args.numbering == "rcm":
         sys.path.insert(0, os.path.join(ROOT, "oracle"))
         import sem_oracle
         gll = np.load(os.path.join(ROOT, "tests", "golden", "gll.npz"))
@@ -1014,7 +1060,7 @@ def main():
                   "vs": "oracle on the whole RCM-numbered mesh", "tolerance": 1e-10}
         log("parity %s" % parity)
         assert parity["rel_l2"] < parity["tolerance"], parity
-    elif not args.no_check:
+    elif check:
         assert torch.isfinite(y).all().item(), "non-finite output"
         if kind == POISSON:
             parity = parity_spot_check(op, y, u, part, p, args.warp)
@@ -1086,7 +1132,8 @@ def main():
             "per_rank_ms_per_step": per_rank_ms,
             "exchange_bytes_per_step_per_rank": 2 * op.exchange_bytes,
             "interface_elements": op.n_iface_elem,
-            "kernel_ms_avg": kern_avg_s * 1e3, "kernel_ms_min": float(np.min(kern_ms)),
+            "kernel_ms_avg": kern_avg_s * 1e3,
+            "kernel_ms_min": float(np.min(kern_ms)) if kern_ms else None,
             "kernel_ms_note": ("avg = mean of the timed actions' HIP-event times, including the "
                                "shader-clock ramp of the first actions (it must match the "
                                "rocprofv3 average); the median is kernel_ms_quartiles[1]"
@@ -1094,12 +1141,13 @@ def main():
                                "avg = HIP events around the K timed actions / K (gaps between "
                                "the launches included; the rocprofv3 averages sum to at most "
                                "it); min / quartiles / max from per-action events of a second, "
-                               "untimed pass"),
+                               "untimed pass (--full)"),
             "step_events": args.step_events,
-            "kernel_ms_quartiles": [float(q) for q in np.percentile(kern_ms, [25, 50, 75])],
-            "kernel_ms_max": float(np.max(kern_ms)),
-            "kernel_ms_series": [round(float(x), 5) for x in kern_ms] if args.kernel_series
-            else None,
+            "kernel_ms_quartiles": [float(q) for q in np.percentile(kern_ms, [25, 50, 75])]
+            if kern_ms else None,
+            "kernel_ms_max": float(np.max(kern_ms)) if kern_ms else None,
+            "kernel_ms_series": [round(float(x), 5) for x in kern_ms]
+            if args.kernel_series and kern_ms else None,
             "host_enqueue_ms_per_step": t_enqueue / args.steps * 1e3,
             "decomposition": op.dd_info(),
             "gflops_kernel": F / kern_avg_s / 1e9,
@@ -1135,7 +1183,7 @@ def main():
     if parity_ranks is not None:
         result["parity_per_rank"] = parity_ranks
         result["parity_interface_per_rank"] = parity_iface
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and kind == POISSON:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline and kind == POISSON:
         log("timing CPU baseline (NumPy oracle of the reference path, child process)...")
         env = dict(os.environ, OMP_NUM_THREADS="1", OPENBLAS_NUM_THREADS="1",
                    MKL_NUM_THREADS="1")
@@ -1384,6 +1432,8 @@ def bench_pcg(args, op, part, nodes, dev, world, rank, ndof_global, t_setup):
         t = torch.tensor([elapsed], dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = t.item()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, "x", x_run, rank, world)
     own = torch.from_numpy(part.owned).to(dev)
     err_num = torch.sum((x_run - xs)[own] ** 2)
     err_den = torch.sum(xs[own] ** 2)

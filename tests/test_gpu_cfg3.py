@@ -54,7 +54,7 @@ def _bench(args, timeout):
 @pytest.mark.timeout(900)
 def test_cfg3_eight_strips_on_one_gpu(gpu, tmp_path):
     res, err = _bench(["--gpus", "8", "--rehearse-one-gpu", "--steps", "3", "--warmup", "1",
-                       "--no-cpu-baseline", "--dump-interface", str(tmp_path),
+                       "--full", "--no-cpu-baseline", "--dump-interface", str(tmp_path),
                        "--deadline", "700"], timeout=800)
     cfg = res["config"]
     assert cfg["ranks_seen"] == 8 and res["n_gpus"] == 8
