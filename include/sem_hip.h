@@ -128,14 +128,16 @@ void sem_ctx_destroy(sem_ctx* ctx);
  *     detJxW [E][n][n][n]; sem_set_geom takes [E][6][n][n][n] in the order
  *     (00, 01, 02, 11, 12, 22);
  *   - sem_apply / sem_apply_dot / sem_diag / sem_assemble / sem_zero_shared /
- *     sem_pcg_solve work as on quadrilaterals (stored geometry, column kernel;
- *     SEM_GEOM_NODAL, SEM_KERNEL_MFMA, node states and the axisymmetric kinds
- *     return SEM_E_NOTIMPL);
+ *     sem_pcg_solve work as on quadrilaterals (stored geometry; the column
+ *     kernels by default, SEM_KERNEL_MFMA at p = 11..16, see sem_set_kernel;
+ *     SEM_GEOM_NODAL, SEM_KERNEL_MFMA at other orders, node states and the
+ *     axisymmetric kinds return SEM_E_NOTIMPL);
  *   - sem_plan_info: [0] workgroups, [1] zero list, [2] 0, [3] 1, [4]
  *     element slots per workgroup, [5] chains along xi0, [6] sub-chain length
  *     cap, [7] launch positions, [8] sub-chains, [9] seam nodes, [10] slotted
  *     writes, [11] plain stores, [12] threads per workgroup, [13] 3, [14]
- *     geometry ready, [15] action kernel (1 row form, 0 three-block),
+ *     geometry ready, [15] action kernel (2 matrix-core form, 1 row form,
+ *     0 three-block),
  *     [16] xi2 faces merged in LDS (z-merge), [17] xi1 faces merged in LDS
  *     too (y-merge): slots per row of the workgroup's slot grid, 0 = off,
  *     [18] template map: every element's node ids are its first node's id +
@@ -253,7 +255,16 @@ int sem_set_geom_mode(sem_ctx* ctx, int mode);
  *  SEM_KERNEL_AUTO (default): COLUMN -- on its seam plan it measured ahead
  *    of MFMA at every order on MI355X; the build knob
  *    SEM_MFMA_MIN_N (default 17: never) restores an MFMA range.
- * The environment variable SEM_KERNEL (0/1/2) sets the initial value. */
+ * On a hexahedral context (ndim = 3) SEM_KERNEL_MFMA selects k_hex_mfma, the
+ * matrix-core form of the hexahedral action on the same chain / seam plan
+ * (all six contractions per element as 16 x 16 tiles of
+ * v_mfma_f64_16x16x4_f64, stored factors), for p = 11..16;
+ * at other orders it returns SEM_E_NOTIMPL.  COLUMN and AUTO keep the
+ * three-block kernel below p = 13 and the row form from p = 13
+ * (SEM_HEX_ROWS honoured); the diagonal always runs the three-block kernel.
+ * The environment variable SEM_KERNEL (0/1/2) sets the initial value; on
+ * hexahedral contexts a value of 1 selects the matrix-core form at
+ * p = 11..16 and is ignored at other orders. */
 #define SEM_KERNEL_COLUMN 0
 #define SEM_KERNEL_MFMA 1
 #define SEM_KERNEL_AUTO 2

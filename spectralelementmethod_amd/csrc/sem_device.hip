@@ -1561,8 +1561,8 @@ int sem_set_kernel(sem_ctx* c, int kernel) {
   if (!c) return fail(SEM_E_INVALID, "null ctx");
   if (kernel != SEM_KERNEL_COLUMN && kernel != SEM_KERNEL_MFMA && kernel != SEM_KERNEL_AUTO)
     return fail(SEM_E_INVALID, "unknown kernel " + std::to_string(kernel));
-  if (kernel == SEM_KERNEL_MFMA && c->ndim == 3)
-    return fail(SEM_E_NOTIMPL, "hexahedra: column kernel only");
+  if (kernel == SEM_KERNEL_MFMA && c->ndim == 3 && (c->n < 12 || c->n > 17))
+    return fail(SEM_E_NOTIMPL, "hexahedra: the MFMA kernel is built for p = 11..16");
   if (kernel == SEM_KERNEL_MFMA && (c->dpn != 1 || c->n > 17))
     return fail(SEM_E_NOTIMPL, "the MFMA kernel needs dofs_per_node == 1 and p <= 16");
   c->kernel = kernel;

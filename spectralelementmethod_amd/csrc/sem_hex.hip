@@ -11,6 +11,7 @@
 
 #include "sem_ctx.h"
 #include "sem_hex.h"
+#include "sem_hex_mfma.h"
 
 using sem::fail;
 using semd::DeviceGuard;
@@ -41,6 +42,10 @@ struct HexState {
   // the action's kernel: k_hex_poisson (three-block, default) or k_hex_rows
   // (row form, SEM_HEX_ROWS=1; the diagonal always runs k_hex_poisson)
   bool rows = true;
+  // the action on the fp64 matrix cores (k_hex_mfma; n = 12..17, on request:
+  // SEM_KERNEL_MFMA at the time of sem_set_map); the diagonal keeps
+  // k_hex_poisson
+  bool mfma = false;
   // xi2 faces between the slots of a workgroup summed in LDS (both kernels;
   // SEM_HEX_ZMERGE=0 turns it off)
   bool zmerge = false;
@@ -560,6 +565,28 @@ int hex_build_plan(const std::vector<uint32_t>& h, int64_t E, int64_t n_node, in
 }
 
 // ---------------------------------------------------------------------------
+// the matrix-core form of the action (HEX_SET / HEX_ACC; set_map turns
+// HexState::mfma on only at the orders it is built for)
+template <int N>
+void launch_hex_mfma(const HexState* H, const semh::HexLaunch& L, int mode, const double* u,
+                     double* y, const double* d_D, hipStream_t st) {
+  if constexpr (N >= semh::HEX_MFMA_MIN_N && N <= semh::HEX_MFMA_MAX_N) {
+    const dim3 g((unsigned)H->n_wg), b(semh::hex_threads(N));
+    if (H->tmap && mode == semh::HEX_SET)
+      hipLaunchKernelGGL((semh::k_hex_mfma<N, semh::HEX_SET, true>), g, b, 0, st, u, y, H->d_map,
+                         H->d_G, d_D, L);
+    else if (H->tmap)
+      hipLaunchKernelGGL((semh::k_hex_mfma<N, semh::HEX_ACC, true>), g, b, 0, st, u, y, H->d_map,
+                         H->d_G, d_D, L);
+    else if (mode == semh::HEX_SET)
+      hipLaunchKernelGGL((semh::k_hex_mfma<N, semh::HEX_SET>), g, b, 0, st, u, y, H->d_map,
+                         H->d_G, d_D, L);
+    else
+      hipLaunchKernelGGL((semh::k_hex_mfma<N, semh::HEX_ACC>), g, b, 0, st, u, y, H->d_map,
+                         H->d_G, d_D, L);
+  }
+}
+
 template <int N>
 int launch_hex_apply(sem_ctx* c, int mode, const double* u, double* y, hipStream_t st) {
   HexState* H = c->hex;
@@ -568,7 +595,9 @@ int launch_hex_apply(sem_ctx* c, int mode, const double* u, double* y, hipStream
   const dim3 g((unsigned)H->n_wg), b(semh::hex_threads(N));
   semh::HexD<N> Dk;
   for (int i = 0; i < N * N; ++i) Dk.d[i] = c->hD[i];
-  if (H->rows && H->tmap && mode == semh::HEX_SET)
+  if (H->mfma && mode != semh::HEX_DIAG)
+    launch_hex_mfma<N>(H, L, mode, u, y, c->d_D, st);
+  else if (H->rows && H->tmap && mode == semh::HEX_SET)
     hipLaunchKernelGGL((semh::k_hex_rows<N, semh::HEX_SET, true>), g, b, 0, st, u, y, H->d_map,
                        H->d_G, c->d_D, L, Dk);
   else if (H->rows && H->tmap && mode == semh::HEX_ACC)
@@ -739,11 +768,17 @@ int launch_hex_geom(sem_ctx* c, const double* nodes, double* GP, double* xph, do
 static_assert(semh::HEX_MAX_N == 17, "HEX_DISPATCH lists n = 2..17");
 
 // workgroups of the element kernel resident per CU (LDS and VGPR bound)
+// (the matrix-core form: of the instantiation that will run, with or without
+// the template map -- their register counts straddle an occupancy step)
 template <int N>
-int hex_wgs_per_cu(bool rows, int* out) {
+int hex_wgs_per_cu(bool rows, bool mfma, bool tmap, int* out) {
   int nb = 0;
   const void* k = rows ? reinterpret_cast<const void*>(&semh::k_hex_rows<N, semh::HEX_SET>)
                        : reinterpret_cast<const void*>(&semh::k_hex_poisson<N, semh::HEX_SET>);
+  if constexpr (N >= semh::HEX_MFMA_MIN_N)
+    if (mfma)
+      k = tmap ? reinterpret_cast<const void*>(&semh::k_hex_mfma<N, semh::HEX_SET, true>)
+               : reinterpret_cast<const void*>(&semh::k_hex_mfma<N, semh::HEX_SET>);
   if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k, semh::hex_threads(N), 0) !=
       hipSuccess) {
     (void)hipGetLastError();
@@ -824,33 +859,17 @@ int set_map(sem_ctx* c, const uint32_t* d_e2n, hipStream_t st) {
         ncu > 0)
       c->n_cu = ncu;
   }
-  int wpc = 0, rc = SEM_OK;
-  HEX_DISPATCH(rc, N, hex_wgs_per_cu, H->rows, &wpc);
-  if (rc) return rc;
-  const int64_t resident = (int64_t)std::max(c->n_cu, 1) * std::max(wpc, 1);
-  HexPlanHost P;
-  rc = hex_build_plan(h, c->n_elem, c->n_node, N, resident, H->zmerge, H->ymerge, P);
-  if (rc) return rc;
-  c->epoch++;
-  c->map_epoch++;
-  H->free_plan();
-  (void)hipFree(H->d_map);
-  H->d_map = nullptr;
-  HIP_TRY(hipMalloc(&H->d_map, count * sizeof(uint32_t)));
-  HIP_TRY(hipMemcpy(H->d_map, h.data(), count * sizeof(uint32_t), hipMemcpyHostToDevice));
-  if ((rc = upload(&H->d_wg_off, P.wg_off)) || (rc = upload(&H->d_wg_len, P.wg_len)) ||
-      (rc = upload(&H->d_elist, P.elist)) || (rc = upload(&H->d_cmask, P.cmask)) ||
-      (rc = upload(&H->d_cflag, P.cflag)) || (rc = upload(&H->d_seam_gid, P.seam_gid)) ||
-      (rc = upload(&H->d_seam_ptr, P.seam_ptr)) || (rc = upload(&H->d_seam_idx, P.seam_idx)) ||
-      (rc = upload(&H->d_zero, P.zero)))
-    return rc;
-  // template map: one offset block shared by every element (structured
-  // numberings); both kernel forms and the diagonal
+  // the matrix-core form on request, where it is built (other orders stay
+  // on the column forms: SEM_KERNEL=1 in the environment reaches every context)
+  const bool mfma = c->kernel == SEM_KERNEL_MFMA && N >= HEX_MFMA_MIN_N && N <= HEX_MFMA_MAX_N;
+  // template map (HexLaunch::ebase / tmpl): does every element's map equal
+  // its first node's id + the offsets of element 0?
+  std::vector<int> tmpl((size_t)N3);
+  std::vector<uint32_t> eb;
+  bool tmap_ok;
   {
     const char* te = std::getenv("SEM_HEX_TMAP");
     bool ok = c->n_elem > 0 && !(te && std::atoi(te) == 0);
-    std::vector<int> tmpl((size_t)N3);
-    std::vector<uint32_t> eb;
     if (ok) {
       for (int64_t i = 0; i < N3 && ok; ++i) {
         const int64_t d = (int64_t)h[i] - (int64_t)h[0];
@@ -864,10 +883,34 @@ int set_map(sem_ctx* c, const uint32_t* d_e2n, hipStream_t st) {
         for (int64_t i = 1; i < N3 && ok; ++i) ok = me[i] == me[0] + (uint32_t)tmpl[(size_t)i];
       }
     }
-    if (ok) {
-      if ((rc = upload(&H->d_ebase, eb)) || (rc = upload(&H->d_tmpl, tmpl))) return rc;
-      H->tmap = true;
-    }
+    tmap_ok = ok;
+  }
+  int wpc = 0, rc = SEM_OK;
+  HEX_DISPATCH(rc, N, hex_wgs_per_cu, H->rows, mfma, tmap_ok, &wpc);
+  if (rc) return rc;
+  const int64_t resident = (int64_t)std::max(c->n_cu, 1) * std::max(wpc, 1);
+  HexPlanHost P;
+  rc = hex_build_plan(h, c->n_elem, c->n_node, N, resident, H->zmerge, H->ymerge, P);
+  if (rc) return rc;
+  c->epoch++;
+  c->map_epoch++;
+  H->free_plan();
+  H->mfma = mfma;
+  (void)hipFree(H->d_map);
+  H->d_map = nullptr;
+  HIP_TRY(hipMalloc(&H->d_map, count * sizeof(uint32_t)));
+  HIP_TRY(hipMemcpy(H->d_map, h.data(), count * sizeof(uint32_t), hipMemcpyHostToDevice));
+  if ((rc = upload(&H->d_wg_off, P.wg_off)) || (rc = upload(&H->d_wg_len, P.wg_len)) ||
+      (rc = upload(&H->d_elist, P.elist)) || (rc = upload(&H->d_cmask, P.cmask)) ||
+      (rc = upload(&H->d_cflag, P.cflag)) || (rc = upload(&H->d_seam_gid, P.seam_gid)) ||
+      (rc = upload(&H->d_seam_ptr, P.seam_ptr)) || (rc = upload(&H->d_seam_idx, P.seam_idx)) ||
+      (rc = upload(&H->d_zero, P.zero)))
+    return rc;
+  // template map: one offset block shared by every element (structured
+  // numberings); every kernel form and the diagonal
+  if (tmap_ok) {
+    if ((rc = upload(&H->d_ebase, eb)) || (rc = upload(&H->d_tmpl, tmpl))) return rc;
+    H->tmap = true;
   }
   H->n_wg = (int64_t)P.wg_off.size();
   H->n_pos = (int64_t)P.elist.size();
@@ -992,15 +1035,15 @@ int plan_info(const sem_ctx* c, int64_t* info, int n_info) {
   // [4] element slots per workgroup, [5] chains (maximal), [6] sub-chain
   // length cap, [7] launch positions, [8] sub-chains, [9] seam nodes,
   // [10] slotted writes, [11] plain stores, [12] threads per workgroup,
-  // [13] ndim (3), [14] geometry ready, [15] action kernel (1 row form,
-  // 0 three-block), [16] z-merge in the plan, [17] y-merge: slots per grid
+  // [13] ndim (3), [14] geometry ready, [15] action kernel (2 matrix-core
+  // form, 1 row form, 0 three-block), [16] z-merge in the plan, [17] y-merge: slots per grid
   // row (0: off), [18] template map
   const int64_t v[] = {H->n_wg,        H->n_zero, 0,
                        1,              H->slots,  H->n_chains,
                        H->chain_len,   H->n_pos,  H->n_subchains,
                        H->n_seam,      H->n_seam_writes, H->n_direct,
                        H->threads,     3,         H->have_G ? 1 : 0,
-                       H->rows ? 1 : 0, H->zmerge ? 1 : 0, H->ymerge ? hex_grid_z(H->N) : 0,
+                       H->mfma ? 2 : H->rows ? 1 : 0, H->zmerge ? 1 : 0, H->ymerge ? hex_grid_z(H->N) : 0,
                        H->tmap ? 1 : 0};
   const int nv = (int)(sizeof(v) / sizeof(v[0]));
   for (int i = 0; i < n_info; ++i) info[i] = i < nv ? v[i] : 0;

@@ -151,8 +151,11 @@ class SEMOperator(object):
         Kernel family of the Poisson action: the LDS column kernel or the
         fp64 matrix-core element kernel (p <= 15); "auto" (default) resolves
         to the library's measured choice (the column kernel: on its seam
-        plan it is ahead of mfma at every order).  See include/sem_hip.h
-        sem_set_kernel.
+        plan it is ahead of mfma at every order).  On hexahedra "mfma" is the
+        matrix-core form of the column plan (k_hex_mfma),
+        built for p = 11..16 (NotImplementedError at other orders); "auto"
+        and "column" keep the three-block / row kernels.  See
+        include/sem_hip.h sem_set_kernel.
     node_state : array-like uint8 [n_node], optional
         For operators that share the output vector with others applied
         before / after it in stream order: NODE_PRIOR marks nodes whose y
@@ -188,9 +191,12 @@ class SEMOperator(object):
             raise ValueError("e2n must have shape [E, %d, %d] or [E, %d, %d, %d]"
                              % ((self.n,) * 5))
         if self.ndim == 3 and (self.dpn != 1 or node_state is not None or
-                               geometry in ("nodal", "reference") or kernel == "mfma"):
+                               geometry in ("nodal", "reference")):
             raise NotImplementedError("hexahedral operators: Poisson (dofs_per_node = 1), "
-                                      "stored geometry, column kernel, no node states")
+                                      "stored geometry, no node states")
+        if self.ndim == 3 and kernel == "mfma" and not 11 <= self.p <= 16:
+            raise NotImplementedError("hexahedral operators: the mfma kernel is built for "
+                                      "p = 11..16")
         self.basis, self.D, self.w, self.Vinv = _basis_arrays(self.p, basis, self.ndim)
         nodes_t = torch.as_tensor(nodes, dtype=torch.float64)
         if nodes_t.dim() != 2 or nodes_t.shape[0] != self.ndim:
@@ -263,8 +269,8 @@ class SEMOperator(object):
                         slots_per_workgroup=v[4], chains=v[5], chain_length_cap=v[6],
                         positions=v[7], subchains=v[8], seam_nodes=v[9], slotted_writes=v[10],
                         plain_stores=v[11], threads=v[12], geometry="stored",
-                        kernel="column", plan="chains-seams",
-                        hex_kernel="rows" if v[15] else "three_block", zmerge=bool(v[16]),
+                        kernel="mfma" if v[15] == 2 else "column", plan="chains-seams",
+                        hex_kernel=("three_block", "rows", "mfma")[v[15]], zmerge=bool(v[16]),
                         ymerge=bool(v[17]), template_map=bool(v[18]),
                         slot_grid=(v[4] // v[17], v[17]) if v[17] else (1, v[4]))
         counts = [x for x in v[8:8 + v[5]]]
