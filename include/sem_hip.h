@@ -551,6 +551,120 @@ int sem_dd_pcg_solve(sem_dd* dd, int op_kind, const double* d_b, double* d_x,
                      const uint8_t* d_dirichlet, double rtol, int max_iter, int check_every,
                      int* iters, double* final_relres, void* stream);
 
+/* ------------------------------------------------------------------ */
+/* Points: location and field evaluation at arbitrary physical points  */
+/* ------------------------------------------------------------------ */
+/* The batched device form of DOFManager.find_elem_containing_point /
+ * interpolate (sem/discrete.py:221-233, 263-280) and Mapping.inv
+ * (sem/mapping.py:146-178), which the reference runs one point at a time
+ * (a sort of every cell centroid per query, then up to 8 Newton steps of
+ * Python barycentric evaluations).  Quadrilaterals and hexahedra,
+ * 1 <= p <= 16 (GLL nodes and barycentric weights of csrc/gll_table.h).
+ * Point arrays are component-major: d_xq / d_xi / d_x_out float64
+ * [ndim][n_pts]; element ids int32 [n_pts]; n_pts < 2^31. */
+typedef struct sem_points sem_points;
+typedef struct sem_pplan sem_pplan;
+
+/* Relative inflation (of its own extent, per axis and side) of an element's
+ * axis-aligned box over its GLL coefficients: a Lagrange interpolant is not
+ * bounded by its nodal hull.  An element is a candidate for a point only
+ * when the point lies in its inflated box. */
+#define SEM_POINTS_BOX_MARGIN 0.25
+/* A located point is accepted when every |xi_k| <= 1 + SEM_POINTS_XI_SLACK
+ * and is then clamped to [-1, 1]. */
+#define SEM_POINTS_XI_SLACK 1e-10
+
+/* d_x_phys: float64 [n_elem][ndim][n^ndim] exactly as sem_geom_fields writes
+ * it; BORROWED (the caller keeps it alive and unchanged).  Builds, per
+ * element, the inflated box and the centroid (mean of the 2^ndim corner
+ * coefficients, Mesh._compute_cell_centroids sem/discrete.py:1108-1113) with
+ * one kernel; the boxes (32 or 48 B per element, never x_phys) are copied to
+ * the host, which lays a uniform grid of about n_elem cells over the mesh
+ * box and lists per cell the elements whose box meets it (CSR, uploaded).
+ * Synchronises `stream`.  SEM_E_INVALID: ndim not 2 or 3, p < 1, n_elem < 1,
+ * NULL pointers, non-finite coordinates; SEM_E_NOTIMPL: p > 16 (checked
+ * before any device call). */
+int sem_points_create(sem_points** out, int ndim, int p, int64_t n_elem, const double* d_x_phys,
+                      int device, void* stream);
+void sem_points_destroy(sem_points* pts);
+
+/* For each point: the candidates of its grid cell, in ascending centroid
+ * distance (the reference's order; ties by element id), each tried with the
+ * reference's Newton (sem/rootfind.py:22-53 as called at sem/mapping.py:171):
+ * xi = 0, at most 8 iterations, stop at |dx|_2 <= 1e-8, Jacobian
+ * sum c l' (x) l (equal to the reference's interpolated nodal J field),
+ * closed-form 2x2 / 3x3 solve.  Deviations from the reference:
+ *  1. a candidate whose Newton does not converge, meets a singular Jacobian
+ *     or a non-finite iterate is skipped (the reference lets SolverFailure
+ *     escape, which is all it returns for points outside the mesh);
+ *  2. acceptance is |xi_k| <= 1 + SEM_POINTS_XI_SLACK, then a clamp to
+ *     [-1, 1] (the reference's strict test can reject a point of the domain
+ *     boundary from every element by one ulp);
+ *  3. a point in no candidate gets elem = -1, xi = NaN, is counted in
+ *     *n_outside (may be NULL), and the call still returns SEM_OK.
+ * A point on a shared face may be given to either neighbour.  Work per point
+ * is bounded by 8 Newton steps times its cell's candidate count.
+ * Synchronises `stream` (the count is read back).  The count's device word
+ * and the "last locate" figures of sem_points_info belong to `pts`: one
+ * sem_points_locate at a time per sem_points (calls from several streams or
+ * threads on one object must be serialised by the caller; invert, map, plan
+ * and eval keep no state in `pts` and may run concurrently). */
+int sem_points_locate(sem_points* pts, int64_t n_pts, const double* d_xq, int32_t* d_elem,
+                      double* d_xi, int64_t* n_outside, void* stream);
+
+/* The same Newton in caller-given elements (Mapping.inv for many points):
+ * d_xi_guess may be NULL (xi = 0).  d_status (uint8, may be NULL): 0 inside
+ * (slack and clamp as above), 1 converged outside [-1, 1]^d (xi as
+ * converged), 2 failed or element id outside [0, n_elem) (xi = NaN; no
+ * memory is indexed with a bad id).  Does not synchronise. */
+int sem_points_invert(sem_points* pts, int64_t n_pts, const double* d_xq,
+                      const int32_t* d_elem_in, const double* d_xi_guess, double* d_xi,
+                      uint8_t* d_status, void* stream);
+
+/* x(xi) in the given elements (Mapping.__call__, sem/mapping.py:141-144; the
+ * evaluator of the Newton residual); NaN for ids outside [0, n_elem). */
+int sem_points_map(sem_points* pts, int64_t n_pts, const int32_t* d_elem, const double* d_xi,
+                   double* d_x_out, void* stream);
+
+/* Buckets a located point set by element (device count, host prefix sum of
+ * the n_elem counts, device fill) and cuts every element's run into items of
+ * at most W points; W = 16 when the touched elements hold 24 points or fewer
+ * on average (four items share a wavefront), else 64.  Points whose id is
+ * outside [0, n_elem) belong to no run.  Holds the permutation and the items;
+ * d_elem is not needed afterwards.  Synchronises `stream`. */
+int sem_points_plan(sem_points* pts, int64_t n_pts, const int32_t* d_elem,
+                    sem_pplan** out, void* stream);
+void sem_points_plan_destroy(sem_pplan* plan);
+
+/* out[c][i] = sum_{jk..} u[c * comp_stride + e2n[elem_i][j][k].. * node_stride]
+ *                        l_j(xi0_i) l_k(xi1_i) ..          (c < ncomp)
+ * (FiniteElement.interpolate of coeffs[..., fe.node_ind],
+ * sem/discrete.py:231-233) for the planned points, in the caller's point
+ * order; d_out float64 [ncomp][n_pts].  Component-major fields: comp_stride =
+ * n_node, node_stride = 1; interleaved DOFs: comp_stride = 1, node_stride =
+ * dpn.  d_e2n: uint32 [n_elem][n^ndim] (the caller's map, as sem_set_map
+ * takes it); d_xi as located.  At xi exactly on a GLL node the basis is the
+ * Kronecker delta (as sem_barycentric_lagrange): no 0/0 reaches the output.
+ * Points in no run get NaN and index no memory at all: a bad element id
+ * cannot cause an out-of-bounds access.  The map's entries are the caller's
+ * obligation: d_u must hold at least max(d_e2n) + 1 nodes per component
+ * (entries up to (ncomp - 1) * comp_stride + max(d_e2n) * node_stride), which
+ * this call cannot check without reading the map; points.PointSet.evaluate
+ * refuses a u of any other size.  Allocates nothing and does not
+ * synchronise (graph-capturable, like sem_apply). */
+int sem_points_eval(sem_pplan* plan, const uint32_t* d_e2n, const double* d_xi, int ncomp,
+                    int64_t comp_stride, int64_t node_stride, const double* d_u, double* d_out,
+                    void* stream);
+
+/* info[0] ndim, [1] p, [2] n_elem, [3..5] grid cells per axis, [6] cells,
+ * [7] CSR entries, [8] most candidates in one cell, [9] / [10] points found /
+ * outside in the last sem_points_locate, [11] Newton iteration cap.
+ * Writes min(n_info, 12) values. */
+int sem_points_info(sem_points* pts, int64_t* info, int n_info);
+/* info[0] points, [1] points in runs, [2] items, [3] touched elements,
+ * [4] lanes per item W, [5] items per workgroup.  min(n_info, 6) values. */
+int sem_points_plan_info(sem_pplan* plan, int64_t* info, int n_info);
+
 #ifdef __cplusplus
 }
 #endif

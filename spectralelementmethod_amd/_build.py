@@ -13,7 +13,7 @@ CSRC = os.path.join(PKG_DIR, "csrc")
 LIB_NAME = "libsem_hip.so"
 LIB_PATH = os.environ.get("SEM_LIB_PATH", os.path.join(PKG_DIR, LIB_NAME))
 SOURCES = ["sem_device.hip", "sem_dd.hip", "sem_sc.hip", "sem_basis.cpp", "sem_hex.hip",
-           "sem_order.cpp"]
+           "sem_order.cpp", "sem_points.hip"]
 # (lo, hi) order ranges of sem_launch.hip, balanced by compile time (the
 # unrolled column kernels grow with n)
 LAUNCH_RANGES = [(2, 5), (6, 8), (9, 9), (10, 11), (12, 13), (14, 15), (16, 16), (17, 17)]
@@ -24,7 +24,10 @@ LAUNCH_RANGES = [(2, 5), (6, 8), (9, 9), (10, 11), (12, 13), (14, 15), (16, 16),
 NO_LICM = ("-mllvm", "-disable-machine-licm")
 LAUNCH_CD_RANGES = [((2, 6), ()), ((7, 7), NO_LICM), ((8, 10), ()), ((11, 13), ()),
                     ((14, 15), ()), ((16, 16), ()), ((17, 17), NO_LICM)]
-DEPS = SOURCES + ["sem_launch.hip", "sem_launch_cd.hip", "sem_internal.h", "sem_kernels.h", "sem_ctx.h", "sem_hex.h", "sem_hex_mfma.h", "gll_table.h",
+# the point location / evaluation kernels (sem_points_launch.hip), per range
+POINTS_RANGES = [(2, 9), (10, 17)]
+DEPS = SOURCES + ["sem_launch.hip", "sem_launch_cd.hip", "sem_points_launch.hip", "sem_points.h",
+                  "sem_internal.h", "sem_kernels.h", "sem_ctx.h", "sem_hex.h", "sem_hex_mfma.h", "gll_table.h",
                   "deo_const.h"]
 ARCH = os.environ.get("SEM_OFFLOAD_ARCH", "gfx950")
 
@@ -78,6 +81,13 @@ def build(force=False, verbose=True, out=None, defines=(), orders=None):
         units.append(("sem_launch_cd.hip", ["-DSEM_N_LO=%d" % lo, "-DSEM_N_HI=%d" % hi,
                                             *flags],
                       os.path.join(objdir, "sem_launch_cd_%d_%d.o" % (lo, hi))))
+
+    for lo, hi in POINTS_RANGES:
+        if orders and (hi < orders[0] or lo > orders[1]):
+            continue
+        lo, hi = (max(lo, orders[0]), min(hi, orders[1])) if orders else (lo, hi)
+        units.append(("sem_points_launch.hip", ["-DSEM_N_LO=%d" % lo, "-DSEM_N_HI=%d" % hi],
+                      os.path.join(objdir, "sem_points_launch_%d_%d.o" % (lo, hi))))
 
     headers = [os.path.join(CSRC, d) for d in DEPS if d.endswith(".h")]
     headers.append(os.path.join(os.path.dirname(PKG_DIR), "include", "sem_hip.h"))

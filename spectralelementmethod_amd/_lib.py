@@ -36,6 +36,8 @@ KERNEL_MFMA = 1
 KERNEL_AUTO = 2
 NODE_PRIOR = 1
 NODE_OTHER = 2
+POINTS_BOX_MARGIN = 0.25
+POINTS_XI_SLACK = 1e-10
 
 # every symbol include/sem_hip.h declares, with (restype, argtypes)
 _i64 = C.c_int64
@@ -102,6 +104,16 @@ SIGNATURES = {
     "sem_dd_diag": (C.c_int, [_vp, C.c_int, _vp, _vp]),
     "sem_dd_pcg_solve": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, C.c_double, C.c_int, C.c_int,
                                    C.POINTER(C.c_int), C.POINTER(C.c_double), _vp]),
+    "sem_points_create": (C.c_int, [C.POINTER(_vp), C.c_int, C.c_int, _i64, _vp, C.c_int, _vp]),
+    "sem_points_destroy": (None, [_vp]),
+    "sem_points_locate": (C.c_int, [_vp, _i64, _vp, _vp, _vp, C.POINTER(_i64), _vp]),
+    "sem_points_invert": (C.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "sem_points_map": (C.c_int, [_vp, _i64, _vp, _vp, _vp, _vp]),
+    "sem_points_plan": (C.c_int, [_vp, _i64, _vp, C.POINTER(_vp), _vp]),
+    "sem_points_plan_destroy": (None, [_vp]),
+    "sem_points_eval": (C.c_int, [_vp, _vp, _vp, C.c_int, _i64, _i64, _vp, _vp, _vp]),
+    "sem_points_info": (C.c_int, [_vp, C.POINTER(_i64), C.c_int]),
+    "sem_points_plan_info": (C.c_int, [_vp, C.POINTER(_i64), C.c_int]),
 }
 
 # sem_exchange_fn / sem_allreduce_fn (include/sem_hip.h)

@@ -21,6 +21,11 @@ them one element at a time.  Here the element loop is one GPU launch:
   ``DOFManagerSC.solve_poisson`` solves the same assembled Poisson system
   matrix-free (Jacobi-PCG on the GPU, no element matrices at all).
 
+* ``DOFManager.interpolate`` / ``find_elem_containing_point``
+  (sem/discrete.py:221-233, 263-280) locate points and evaluate fields with
+  the batched device kernels of ``points.PointLocator`` (one point as in the
+  reference, or many at once).
+
 Node reorderings (RCM, static-condensation ordering) are host-side setup and
 reproduce the reference's permutations exactly.
 """
@@ -30,9 +35,14 @@ import numpy as np
 from scipy import sparse
 
 from .geometry import NCube, Quadrilateral
-from .mapping import Mapping, OutsideDomain  # noqa: F401
+from .mapping import Mapping
 
 _CELL_CHUNK = 4096
+
+
+class OutsideDomain(Exception):
+    """Physical point outside the mesh (sem/discrete.py:19-23; a class of its
+    own, distinct from ``mapping.OutsideDomain``, as in the reference)."""
 
 
 class Static_COO_Matrix(object):
@@ -490,11 +500,46 @@ class DOFManager(object):
         vals[..., e2n] = out
         return vals
 
+    def point_locator(self):
+        """Device point locator of this mesh (``points.PointLocator``), cached
+        per mesh version like ``operator()``."""
+        return self.operator().point_locator()
+
     def interpolate(self, coeffs, x_phys):
-        raise NotImplementedError("point location (sem/discrete.py:221-233) is out of scope")
+        """Interpolate global coefficients ``coeffs[..., node]`` at physical
+        points (sem/discrete.py:221-233).  One point [ndim] returns the value
+        (shape ``coeffs.shape[:-1]``) and raises ``OutsideDomain`` outside
+        the mesh, as the reference; additionally [ndim, M] returns [..., M]
+        with NaN at points outside.  Location and evaluation run on the
+        device (``point_locator()``).
+
+        ``coeffs`` and ``x_phys`` are host arrays, as in the reference, and
+        every call locates its points and builds an evaluation plan anew.  To
+        evaluate many fields (or time steps) at one point set, or to keep
+        points and fields on the device, use
+        ``ps = point_locator().locate(x)`` once and ``ps.evaluate(u)`` per
+        field (``points.PointSet``)."""
+        x = np.asarray(x_phys, dtype=np.float64)
+        single = x.ndim == 1
+        coeffs = np.asarray(coeffs, dtype=np.float64)
+        ps = self.point_locator().locate(x.reshape(self._mesh.ndim, -1))
+        if single and ps.n_outside:
+            raise OutsideDomain("Point {} appears outside the domain of the mesh.".format(x))
+        vals = ps.evaluate(coeffs)
+        return vals[..., 0] if single else vals
 
     def find_elem_containing_point(self, point):
-        raise NotImplementedError("point location (sem/discrete.py:263-280) is out of scope")
+        """(FiniteElement, x_param) of the element containing ``point``
+        (sem/discrete.py:263-280), located on the device; raises
+        ``OutsideDomain`` outside the mesh.  One host point per call; for
+        many points ``point_locator().locate(x)`` returns all element ids
+        and parametric coordinates in one launch."""
+        point = np.asarray(point, dtype=np.float64).reshape(self._mesh.ndim)
+        ps = self.point_locator().locate(point.reshape(-1, 1))
+        if ps.n_outside:
+            raise OutsideDomain("Point {} appears outside the domain of the mesh.".format(point))
+        fe = self.get_finite_element(int(ps.elem[0].item()), x_phys=True, Jacobian=True)
+        return fe, ps.xi[:, 0].cpu().numpy()
 
 
 def band_order(A):
@@ -881,6 +926,13 @@ class FiniteElement(object):
 
     def local(self, arr):
         return arr[self.node_ind]
+
+    def interpolate(self, coeffs, x_param):
+        """Element-local coefficients at a parametric point
+        (sem/discrete.py:670-672), on the host."""
+        x_param = np.asarray(x_param, dtype=np.float64)
+        assert (x_param >= -1).all() and (x_param <= 1).all()
+        return self._basis.interpolate(coeffs, x_param)
 
     def gradient(self, coeffs):
         """Physical gradient invJ^T . grad_xi (sem/discrete.py:680-684);

@@ -225,6 +225,7 @@ class SEMOperator(object):
                 _lib.check(self._lib.sem_set_map_shared(ctx, _lib.tptr(self.e2n), _lib.tptr(st),
                                                         _lib.stream_ptr()))
         self._geom_ready = set()
+        self._locator = None
 
     @staticmethod
     def _to_map(e2n):
@@ -243,6 +244,7 @@ class SEMOperator(object):
 
     # ------------------------------------------------------------------
     def close(self):
+        self._locator = None  # lives on while a PointSet refers to it
         if getattr(self, "_solver", None) and self._solver[0] is not None:
             self._solver[0].close()
         self._solver = None
@@ -346,6 +348,14 @@ class SEMOperator(object):
                 _lib.tptr(out["J"]), _lib.tptr(out["invJ"]), _lib.tptr(out["detJ"]),
                 _lib.tptr(out["detJxW"]), self._stream(stream)))
         return out
+
+    def point_locator(self):
+        """The ``points.PointLocator`` of this operator's mesh (built once):
+        locate physical points and evaluate fields there on the device."""
+        if self._locator is None:
+            from .points import PointLocator
+            self._locator = PointLocator(self)
+        return self._locator
 
     # ------------------------------------------------------------------
     def _vec(self, v, name):
