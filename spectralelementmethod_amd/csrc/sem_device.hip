@@ -291,7 +291,12 @@ int ensure_gp(sem_ctx* c, int op_kind, hipStream_t st) {
   const int slot = gp_slot(op_kind);
   if (!c->d_GP[slot]) {
     const int ncomp = sem_op_ncomp(op_kind);
-    const size_t bytes = (size_t)c->n_slots * ncomp * c->n * c->lw * sizeof(double);
+    // + WAVE: the column kernels address the factors per lane, and the idle
+    // lanes of a wavefront (lane >= lw, orders that do not divide 64) read up
+    // to WAVE - lw entries past their slot's block -- past the array in the
+    // last slot (values unused)
+    const size_t bytes =
+        ((size_t)c->n_slots * ncomp * c->n * c->lw + WAVE) * sizeof(double);
     HIP_TRY(hipMalloc(&c->d_GP[slot], bytes));
     HIP_TRY(hipMemsetAsync(c->d_GP[slot], 0, bytes, st));
   }
@@ -1717,7 +1722,9 @@ int sem_apply(sem_ctx* c, int op_kind, const double* u, double* y, int flags, vo
   if (op_kind == SEM_OP_AXISYM_NS_JVP && !c->lin_valid)
     return fail(SEM_E_STATE, "no linearisation: apply SEM_OP_AXISYM_NS with SEM_APPLY_LINEARIZE first");
   if (lin && !c->d_lin) {
-    HIP_TRY(hipMalloc(&c->d_lin, (size_t)c->n_slots * 5 * c->n * c->lw * sizeof(double)));
+    // + WAVE: idle lanes of the last slot, as in ensure_gp
+    HIP_TRY(hipMalloc(&c->d_lin,
+                      ((size_t)c->n_slots * 5 * c->n * c->lw + WAVE) * sizeof(double)));
     c->epoch++;
   }
   DeviceGuard g(c->device);
