@@ -1,5 +1,5 @@
 // Operator context of libsem_hip.so and the helpers shared by the C ABI
-// (sem_device.hip) and the per-order launch units (sem_launch.hip, compiled
+// (sem_device.hip, sem_hex.hip) and the per-order launch units (sem_launch.hip, compiled
 // once per range of orders so the kernel instantiations build in parallel).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -12,6 +12,7 @@
 
 #include "sem_internal.h"
 #include "sem_kernels.h"
+#include "sem_plan.h"
 
 #define HIP_TRY(expr)                                                                  \
   do {                                                                                 \
@@ -21,47 +22,6 @@
   } while (0)
 
 using semk::BLOCK;
-
-constexpr int MAX_COLOURS = 8;  // + one trailing all-atomic class
-// AUTO choice of the seam plan (Poisson column kernel), from the MI355X A/B
-// of profiles/r02/seams2 (ms per action, colour launches -> seams; cpc =
-// chains per colour): it wins where a colour launch is a few generations of
-// resident workgroups or less -- p = 16 198^2 (cpc 1,633) 0.164 -> 0.134,
-// p = 12 263^2 0.139 -> 0.114, p = 10 316^2 (1,296) 0.158 -> 0.128, p = 9
-// 351^2 (1,297) 0.120 -> 0.113, p = 8 512^2 (2,342) 0.185 -> 0.179, 384^2
-// (1,372) 0.107 -> 0.095, 128 x 1024 (1,171; one rank's strip of the
-// 8-GPU split) 0.098 -> 0.089, 256^2 (585) 0.0635 -> 0.0477, p = 6 256^2
-// (488) 0.040 -> 0.030, p = 4 395^2 (815) 0.045 -> 0.036 -- and loses where
-// the colour launches stream many generations and the seams are a large
-// share of the nodes: p = 8 1024^2 (9,365) 0.640 -> 0.668, p = 6 527^2
-// (1,928) 0.118 -> 0.122, p = 4 790^2 (3,250) 0.113 -> 0.129, p = 2 1581^2
-// 0.132 -> 0.161.
-// Two DOFs per node (axisymmetric block, p = 6, profiles/r02/final/
-// axisym_seams): 128^2 (cpc 114) 0.0441 -> 0.0236, 512^2 (cpc 1,820) 0.227
-// -> 0.274 (the nodal kernel's seam instantiation runs 1 wave per SIMD
-// instead of 2).
-// AUTO of the block layout (sem_device.hip groups_blocks, 4 rounds): only
-// where the mesh still has this many chains with it.  Measured on MI355X,
-// ms per action, consecutive groups -> blocks (profiles/r03/sweep): the
-// axisymmetric Stokes block at 512^2, p = 6 (1,920 block chains) 0.302 ->
-// 0.257; Poisson p = 8 1024^2 (9,472) 0.684 -> 0.671, 395^2 (1,481) 0.106
-// -> 0.107, p = 6 527^2 (1,980) 0.118 -> 0.122, p = 12 263^2 0.132 ->
-// 0.151, p = 16 198^2 0.139 -> 0.188, 256^2 p = 8 0.046 -> 0.056.
-inline int64_t block_min_chains(int n, int dpn) {
-  (void)n;
-  return dpn == 2 ? 1024 : 4096;
-}
-inline bool seam_auto(int n, int64_t chains_per_colour, int dpn = 1, bool blocks = false) {
-  // block layout: the seams are a few % of the nodes (every R-th node row and
-  // every 4*EPW-th column) -- 1024^2 p = 8: R = 4 seams 0.671, colours 0.692,
-  // consecutive groups 0.684 ms (profiles/r03/blocks_ab.txt)
-  if (blocks && dpn == 1) return true;
-  if (dpn == 2) return chains_per_colour <= 512;
-  // n = 7 (p = 6 at 527^2, 1,929 chains per colour; profiles/r04/p6/):
-  // nodal seams 0.099-0.100 against nodal colours 0.106-0.111 and stored
-  // colours 0.118-0.120 ms per action; stored seams 0.116-0.118
-  return n >= 11 || chains_per_colour <= 1024 || ((n >= 9 || n == 7) && chains_per_colour <= 2400);
-}
 
 struct HexState;  // the 3-D (hexahedral) path, sem_hex.hip
 
@@ -117,7 +77,7 @@ struct sem_ctx {
   // seam plan of the Poisson column kernel (SeamPlan, sem_kernels.h)
   bool blocks = false;       // block layout of the chains (groups_blocks)
   int64_t row_carries = 0;
-  bool round_sync = true;  // a chain writes some node in two rounds (Plan::round_rmw)
+  bool round_sync = true;  // a chain writes some node in two rounds (Plan::round_sync)
   bool seam = false;
   bool seam_dot = false;    // sem_apply_dot fuses u.y into the seam plan's launches
   bool defer_seam_sum = false;  // sem_apply leaves the seam sum to the caller (sem_dd's fused finish)
@@ -158,6 +118,17 @@ struct DeviceGuard {
 };
 
 inline hipStream_t S(void* s) { return reinterpret_cast<hipStream_t>(s); }
+
+// replaces the device array *dst by a copy of v (null when v is empty)
+template <typename T>
+int upload(T** dst, const std::vector<T>& v) {
+  (void)hipFree(*dst);
+  *dst = nullptr;
+  if (v.empty()) return SEM_OK;
+  HIP_TRY(hipMalloc(dst, v.size() * sizeof(T)));
+  HIP_TRY(hipMemcpy(*dst, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
+  return SEM_OK;
+}
 
 // even-odd halves of D (row-major h[m*N + r]); see DEO in sem_kernels.h
 template <int N>

@@ -16,6 +16,7 @@
 using sem::fail;
 using semd::DeviceGuard;
 using semd::grid_for;
+using semd::upload;
 
 struct HexState {
   int N = 0, slots = 0, threads = 0, nbc = 0;
@@ -90,16 +91,6 @@ int hex_check_order(int n) {
   if (n < semh::HEX_MIN_N || n > semh::HEX_MAX_N)
     return fail(SEM_E_NOTIMPL, "hexahedral kernels are built for orders 1.." +
                                    std::to_string(semh::HEX_MAX_N - 1));
-  return SEM_OK;
-}
-
-template <typename T>
-int upload(T** dst, const std::vector<T>& v) {
-  (void)hipFree(*dst);
-  *dst = nullptr;
-  if (v.empty()) return SEM_OK;
-  HIP_TRY(hipMalloc(dst, v.size() * sizeof(T)));
-  HIP_TRY(hipMemcpy(*dst, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
   return SEM_OK;
 }
 

@@ -8,15 +8,12 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/sem_hip.h"
+#include "sem_error.h"
 
 #define SEM_MAX_ORDER 16
 #define SEM_MAXN (SEM_MAX_ORDER + 1)
 
 namespace sem {
-
-// thread-local error message behind sem_last_error()
-void set_error(const std::string& msg);
-int fail(int code, const std::string& msg);
 
 // host basis helpers (sem_basis.cpp)
 int gll_table(int p, double* nodes, double* bary, double* quad);

@@ -39,41 +39,18 @@
 #include <utility>
 
 #include "sem_internal.h"
+#include "sem_plan.h"
 
 namespace semk {
 
-constexpr int WAVE = 64;
 constexpr int BLOCK = 256;
-// Groups per chain round = wavefronts per workgroup: 4.  At n = 17 the
-// colour launches ran faster with 2-wave chains (p = 16 at 1e7 DOF: 0.165
-// against 0.173 ms, profiles/r02/variants), but AUTO takes the seam plan
-// there (one launch), on which 4-wave chains are ahead: 0.131
-// against 0.136 ms (profiles/r02/final/chain_width).  SEM_CHAIN_WAVES
-// (diagnostic builds) forces one value for every order.
-#ifdef SEM_CHAIN_WAVES
-constexpr int chain_waves_of(int) { return SEM_CHAIN_WAVES; }
-#else
-constexpr int chain_waves_of(int) { return 4; }
-#endif
+// WAVE, chain_waves_of, the packed map entry (CODE_SHIFT, GID_MASK, W_*): sem_plan.h
 template <int N>
 struct ChainWaves {
   static constexpr int value = chain_waves_of(N);
   static constexpr int block = value * WAVE;
 };
 constexpr int MAXN = 17;
-
-// packed map entry = gid | code << CODE_SHIFT
-constexpr int CODE_SHIFT = 28;
-constexpr uint32_t GID_MASK = (1u << CODE_SHIFT) - 1u;
-constexpr uint32_t W_STORE = 0;   // first writer: y = v   (y += v in accumulate mode)
-constexpr uint32_t W_RMW = 1;     // later writer: y += v (no concurrent writer)
-constexpr uint32_t W_SKIP = 2;    // value merged into another lane / padding
-constexpr uint32_t W_ATOMIC = 3;  // fallback
-constexpr uint32_t W_MERGE = 4;   // add the next lane's value before writing
-constexpr uint32_t W_CARRY = 8;   // add the value handed over by the previous group
-// SKIP | CARRY: row n-1 entry whose value the same lane adds to row 0 of its
-// next round (block layout): not written by this round
-constexpr uint32_t W_ROWCARRY = W_SKIP | W_CARRY;
 
 #ifndef SEM_POISSON_MIN_WAVES
 #define SEM_POISSON_MIN_WAVES 0  // 0: per-order choice (PoissonMinWaves)
@@ -720,22 +697,12 @@ struct MapRef {
   const uint16_t* __restrict__ p16;  // [slot][r][lane] (gid - base) | code << 12
   const uint32_t* __restrict__ base;  // [slot][r]
 };
-constexpr uint32_t M16_OFF_MASK = 0xFFFu;
-constexpr uint32_t M16_WIDE = 0xFFFFFFFFu;  // base[slot][0]: this group uses the 32-bit map
-constexpr int M16_CODE_SHIFT = 12;
-
-// orders with pattern-table (PAT) kernels (SEM_MAP_PATTERN_N, a bit per n;
-// the host builds a table only for these): every order from n = 3 --
-// measured faster at p = 4 / 6 / 8 / 10 / 12 / 14 / 16.  The
-// pattern id sits in the top 4 bits of bases 1..id_rows (min(4, n - 1)):
-// up to 16^id_rows patterns.
-#ifndef SEM_MAP_PATTERN_N
-#define SEM_MAP_PATTERN_N 0x3FFF8u
-#endif
+// M16_OFF_MASK, M16_WIDE, M16_CODE_SHIFT and the orders with pattern-table
+// (PAT) kernels (SEM_MAP_PATTERN_N): sem_plan.h
 template <int N>
 struct PatternMap {
-  static constexpr bool value = N >= 3 && ((SEM_MAP_PATTERN_N >> N) & 1u);
-  static constexpr int id_rows = N - 1 < 4 ? N - 1 : 4;
+  static constexpr bool value = map_pattern_order(N);
+  static constexpr int id_rows = map_pattern_id_rows(N);
 };
 
 template <int N, bool M16 = false, bool LD = false, bool PAT = false>
@@ -805,10 +772,7 @@ __device__ __forceinline__ void load_map(const MapRef& m, int64_t g, int lane, b
 // the data, only the loaded dwords until MapTouch::done, which an empty asm
 // consumes at the end of the round (a load whose value is unused would be
 // dropped; consuming it earlier would wait for it).  The next round's
-// load_map then finds its lines in L2.
-#ifndef SEM_MAP_TOUCH
-#define SEM_MAP_TOUCH 0
-#endif
+// load_map then finds its lines in L2.  (Default 0: sem_plan.h.)
 template <int N>
 struct MapTouch {
   static constexpr int LW = Tile<N>::LW;

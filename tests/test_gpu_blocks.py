@@ -1,5 +1,5 @@
 """The block layout of the chain plans (groups_blocks in
-csrc/sem_device.hip, the row carry in chain_emit, csrc/sem_kernels.h).
+csrc/sem_plan.cpp, the row carry in chain_emit, csrc/sem_kernels.h).
 
 On a structured numbering a chain is R stacked element lines x 4 groups, and
 the node row between two rounds is handed from round to round in registers

@@ -1,4 +1,4 @@
-"""The 16-bit map's pattern table (csrc/sem_device.hip build_map_patterns,
+"""The 16-bit map's pattern table (csrc/sem_plan.cpp build_map_patterns,
 the PAT kernels of csrc/sem_kernels.h): on a structured
 numbering the groups share a few entry patterns and the PAT kernels must
 give the per-group map's result bit for bit -- the entries they assemble

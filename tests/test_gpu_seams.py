@@ -156,7 +156,7 @@ def test_mfma17_seams_match_colour_launches(gpu, gll, monkeypatch, nex, ney):
 @pytest.mark.parametrize("geometry", ["nodal", "stored"])
 def test_chain_swizzle_is_bitwise_neutral(gpu, monkeypatch, geometry):
     """The planner's XCD-contiguous chain order (chain_swizzle in
-    csrc/sem_device.hip, seam launches of <= 2,400 chains) only permutes the
+    csrc/sem_plan.cpp, seam launches of <= 2,400 chains) only permutes the
     chain blocks of the packed arrays: the action equals the unpermuted
     plan's bit for bit, with nodal and with stored (packed by element
     position) factors."""
