@@ -665,6 +665,104 @@ int sem_points_info(sem_points* pts, int64_t* info, int n_info);
  * [4] lanes per item W, [5] items per workgroup.  min(n_info, 6) values. */
 int sem_points_plan_info(sem_pplan* plan, int64_t* info, int n_info);
 
+/* ------------------------------------------------------------------ */
+/* Faces: normals, surface integrals and Neumann loads on element faces */
+/* ------------------------------------------------------------------ */
+/* The batched device form of SubMapping / SubFiniteElement
+ * (sem/mapping.py:184-272, sem/discrete.py:708-775), which the reference
+ * builds as one Python object per face (its 3-D normal is unfinished:
+ * _compute_normal_vec drops the cross product).  Quadrilaterals and
+ * hexahedra, 1 <= p <= 16, isoparametric.
+ *
+ * Conventions (the reference's _subface_slice, sem/mapping.py:19-76, and
+ * SubMapping._tangents, :233-256):
+ *   - face id = 2 * axis + side; axis indexes the element array's axes (xi0
+ *     first), side 0 is xi = -1, side 1 is xi = +1;
+ *   - nf = n^(ndim-1) nodes per face, index q;
+ *   - 2-D faces run counter-clockwise round the element: on faces 0 and 3
+ *     q runs against the element's own index, on faces 1 and 2 along it;
+ *   - 3-D faces: q = q0 * n + q1; on a side-1 face (q0, q1) index the axes
+ *     (axis+1, axis+2) mod 3 in this cyclic order, on a side-0 face the axes
+ *     (axis+2, axis+1) mod 3, the reverse order;
+ *   - tangents are the columns of J (J[c][i] = d x_c / d xi_i) of the face's
+ *     axes in that order, at the face nodes; the 2-D tangent is negated on
+ *     faces 0 and 3;
+ *   - n_dS = (t_y, -t_x) in 2-D, t0 x t1 in 3-D: outward on every face;
+ *   - dS = |n_dS|, unit_normal = n_dS / dS, dSxW = dS times the tensor of the
+ *     1-D quadrature weights on the face.
+ * Face arrays: vectors float64 [F][ndim][nf], scalars [F][nf], matrices
+ * [F][ndim][ndim][nf], node ids uint32 [F][nf]. */
+typedef struct sem_faces sem_faces;
+
+/* d_x_phys: float64 [n_elem][ndim][n^ndim] exactly as sem_geom_fields writes
+ * it; d_e2n: uint32 [n_elem][n^ndim]; h_elem / h_face: the n_faces (element,
+ * face) pairs (a pair may repeat; n_faces == 0 is valid); h_D: the 1-D
+ * differentiation matrix [n][n] (sem_diff_matrix), h_w: the n quadrature
+ * weights.  Every pair is checked on the host before any device call:
+ * SEM_E_INVALID for an element id outside [0, n_elem), a face >= 2 * ndim,
+ * ndim not 2 or 3, p < 1, NULL arrays, n_faces * nf >= 2^31; SEM_E_NOTIMPL for
+ * p > 16.  One kernel (one workgroup per face) computes and stores per face
+ * node x, J (the derivative along the face's normal axis taken with the first
+ * or last row of D), invJ, detJ, n_dS, dSxW and the global node id in face
+ * order; the node ids are read back and the host lists the distinct boundary
+ * nodes (ascending) with the CSR of their (face, q) contributions in
+ * ascending (face, q) order.  Nothing is borrowed after the call returns.
+ * Synchronises `stream`. */
+int sem_faces_create(sem_faces** out, int ndim, int p, int64_t n_elem, const double* d_x_phys,
+                     const uint32_t* d_e2n, int64_t n_faces, const int32_t* h_elem,
+                     const uint8_t* h_face, const double* h_D, const double* h_w, int device,
+                     void* stream);
+void sem_faces_destroy(sem_faces* faces);
+
+/* Copies of the stored face fields (SubFiniteElement.x_phys / n_dS / dS /
+ * dSxW / unit_normal / node_ind, SubMapping.J / invJ / detJ); any output may
+ * be NULL.  invJ[i][j] = d xi_i / d x_j.  One launch, no synchronisation. */
+int sem_faces_geometry(sem_faces* faces, double* d_x, double* d_n_dS, double* d_dS,
+                       double* d_dSxW, double* d_unit, uint32_t* d_node_ind, double* d_J,
+                       double* d_invJ, double* d_detJ, void* stream);
+
+/* Physical gradient of the parent element's interpolant at the face nodes,
+ * grad_j = sum_i invJ[i][j] du/dxi_i (FiniteElement.gradient sliced to the
+ * face, sem/discrete.py:771-774), d_grad [ncomp][F][ndim][nf], and its
+ * product with the unit normal, d_dudn [ncomp][F][nf]; either may be NULL.
+ * u is read as u[c * comp_stride + e2n[..] * node_stride] (sem_points_eval's
+ * strides); d_e2n is the map given at create.  d_u's size is the caller's
+ * obligation, as in sem_points_eval; faces.FaceSet refuses a u of any other
+ * size.  ncomp <= 65535.  One launch; allocates nothing and does not
+ * synchronise (graph-capturable). */
+int sem_faces_gradient(sem_faces* faces, const uint32_t* d_e2n, int ncomp, int64_t comp_stride,
+                       int64_t node_stride, const double* d_u, double* d_grad, double* d_dudn,
+                       void* stream);
+
+/* d_per_face[c][f] = sum_q d_vals[c][f][q] dSxW[f][q]
+ * (SubFiniteElement.integrate, sem/discrete.py:768-769) and d_total[c] =
+ * sum_f of these; either output may be NULL (d_per_face only up to ncomp =
+ * 8: the handle's own scratch then holds the per-face values).  Fixed-order
+ * two-stage sum (per face, then one workgroup per component over the faces):
+ * bitwise repeatable.  With no faces the totals are 0 and nothing else is
+ * written.  Allocates nothing and does not synchronise. */
+int sem_faces_integrate(sem_faces* faces, int ncomp, const double* d_vals, double* d_per_face,
+                        double* d_total, void* stream);
+
+/* The same sums of grad u . unit_normal, without writing the gradient out:
+ * the flux of u through every face and through the whole list. */
+int sem_faces_flux(sem_faces* faces, const uint32_t* d_e2n, int ncomp, int64_t comp_stride,
+                   int64_t node_stride, const double* d_u, double* d_per_face, double* d_total,
+                   void* stream);
+
+/* The Neumann load vector: d_out[node] (+)= sum d_vals[f][q] dSxW[f][q] over
+ * the (f, q) entries of each distinct boundary node, one thread per node over
+ * its CSR row; no atomics, bitwise deterministic; nodes on no listed face are
+ * untouched in both modes.  d_out holds n_node entries: SEM_E_INVALID when a
+ * face node id (known from create) is >= n_node.  Does not synchronise. */
+int sem_faces_assemble(sem_faces* faces, const double* d_vals, double* d_out, int64_t n_node,
+                       int accumulate, void* stream);
+
+/* info[0] ndim, [1] p, [2] faces, [3] nf, [4] distinct boundary nodes,
+ * [5] longest CSR row, [6] largest node id on a face (-1 with no faces).
+ * Writes min(n_info, 7) values. */
+int sem_faces_info(sem_faces* faces, int64_t* info, int n_info);
+
 #ifdef __cplusplus
 }
 #endif

@@ -114,6 +114,15 @@ SIGNATURES = {
     "sem_points_eval": (C.c_int, [_vp, _vp, _vp, C.c_int, _i64, _i64, _vp, _vp, _vp]),
     "sem_points_info": (C.c_int, [_vp, C.POINTER(_i64), C.c_int]),
     "sem_points_plan_info": (C.c_int, [_vp, C.POINTER(_i64), C.c_int]),
+    "sem_faces_create": (C.c_int, [C.POINTER(_vp), C.c_int, C.c_int, _i64, _vp, _vp, _i64, _vp, _vp,
+                                   _dp, _dp, C.c_int, _vp]),
+    "sem_faces_destroy": (None, [_vp]),
+    "sem_faces_geometry": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "sem_faces_gradient": (C.c_int, [_vp, _vp, C.c_int, _i64, _i64, _vp, _vp, _vp, _vp]),
+    "sem_faces_integrate": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp]),
+    "sem_faces_flux": (C.c_int, [_vp, _vp, C.c_int, _i64, _i64, _vp, _vp, _vp, _vp]),
+    "sem_faces_assemble": (C.c_int, [_vp, _vp, _vp, _i64, C.c_int, _vp]),
+    "sem_faces_info": (C.c_int, [_vp, C.POINTER(_i64), C.c_int]),
 }
 
 # sem_exchange_fn / sem_allreduce_fn (include/sem_hip.h)

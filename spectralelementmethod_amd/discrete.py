@@ -21,6 +21,14 @@ them one element at a time.  Here the element loop is one GPU launch:
   ``DOFManagerSC.solve_poisson`` solves the same assembled Poisson system
   matrix-free (Jacobi-PCG on the GPU, no element matrices at all).
 
+* ``DOFManager.boundary_elements`` / ``FiniteElement.sub_fe`` yield
+  ``SubFiniteElement`` objects (sem/discrete.py:211-219, 699-775) that are
+  views of one batched ``faces.FaceSet``: normals, surface quadrature and
+  face gradients of all faces come from the device kernels of
+  csrc/sem_faces.hip; ``DOFManager.boundary_face_set(name)`` gives the whole
+  named boundary as one ``FaceSet`` (surface integrals, fluxes, Neumann
+  loads on the device).
+
 * ``DOFManager.interpolate`` / ``find_elem_containing_point``
   (sem/discrete.py:221-233, 263-280) locate points and evaluate fields with
   the batched device kernels of ``points.PointLocator`` (one point as in the
@@ -166,6 +174,7 @@ class Mesh(object):
         self._boundary_id_lookup = {}
         self._boundary_map = {}
         self._boundary_cells = []
+        self._bnd_version = 0      # bumped whenever a boundary side is recorded
         self._adj = None           # [E, n_sides] neighbour cell per side, -1 on a boundary
         self._e2n = None
         self.condensed = False
@@ -280,6 +289,55 @@ class Mesh(object):
         cell = self._boundary_map.setdefault(cell_number, {})
         cell.setdefault(bnd_id, []).append(Mesh.BoundaryData(ndim, index))
         self._boundary_cells[bnd_id].add(cell_number)
+        self._bnd_version += 1
+
+    def exterior_faces(self):
+        """(elem int32 [F], face uint8 [F]) of every cell side that belongs
+        to one cell only, cells ascending, then faces ascending (face =
+        2 * axis + side).  Two sides are the same when their sorted corner
+        node ids are equal; host only, quadrilaterals and hexahedra."""
+        e2n = self.element_map()
+        E, d = e2n.shape[0], e2n.ndim - 1
+        if d not in (2, 3):
+            raise NotImplementedError("exterior_faces: quadrilaterals and hexahedra")
+        n = e2n.shape[1]
+        corner = np.ix_(*([[0, n - 1]] * d))
+        c = e2n[(slice(None),) + corner].astype(np.int64)              # [E, 2, 2(, 2)]
+        keys = np.stack([np.sort(np.take(c, side, axis=1 + ax).reshape(E, -1), axis=1)
+                         for ax in range(d) for side in (0, 1)], axis=1)  # [E, 2d, 2^(d-1)]
+        flat = keys.reshape(E * 2 * d, -1)
+        _, inv, count = np.unique(flat, axis=0, return_inverse=True, return_counts=True)
+        once = np.flatnonzero(count[inv.ravel()] == 1)
+        return (once // (2 * d)).astype(np.int32), (once % (2 * d)).astype(np.uint8)
+
+    def tag_boundary(self, name, elem, face):
+        """Record the sides (elem[k], face[k]) as part of the boundary
+        ``name`` (created when new) through ``add_boundary_cell``."""
+        elem = np.asarray(elem).ravel()
+        face = np.asarray(face).ravel()
+        if elem.shape != face.shape:
+            raise ValueError("one face id per element id expected")
+        if elem.size and (elem.min() < 0 or elem.max() >= self.n_cells or face.min() < 0
+                          or face.max() >= 2 * self.ndim):
+            raise ValueError("tag_boundary: element or face id out of range")
+        bid = self._boundary_id_lookup.get(name)
+        if bid is None:
+            bid = self.new_boundary(name)
+        for e, f in zip(elem.tolist(), face.tolist()):
+            self.add_boundary_cell(int(e), bid, self.ndim - 1, int(f))
+        return bid
+
+    def boundary_faces(self, name):
+        """(elem int32 [F], face uint8 [F]) of the boundary ``name`` in the
+        order ``DOFManager.boundary_elements`` visits them: cells ascending
+        (``cells_on_boundary``), then each cell's recorded order."""
+        bid = self._boundary_id_lookup[name]
+        elem, face = [], []
+        for i in sorted(self._boundary_cells[bid]):
+            for bd in self._boundary_map[i].get(bid, []):
+                elem.append(i)
+                face.append(bd.index)
+        return np.asarray(elem, dtype=np.int32), np.asarray(face, dtype=np.uint8)
 
     def _flush(self):
         if self._maps:
@@ -399,6 +457,7 @@ class DOFManager(object):
         self._op = None
         self._op_version = None
         self._fields = None
+        self._face_sets = {}
         if rcm_order:
             self._reorder_nodes_rcm()
 
@@ -485,9 +544,49 @@ class DOFManager(object):
         for i in range(self._mesh.n_cells):
             yield FiniteElement(self, self._mesh.get_cell(i), compute_flags, i)
 
+    # ------------------------------------------------------------------ faces
+    def _face_set(self, key, pairs):
+        """FaceSet cached per key, mesh numbering and boundary record."""
+        op = self.operator()
+        stamp = (self._mesh.version, self._mesh._bnd_version, id(op))
+        hit = self._face_sets.get(key)
+        if hit is None or hit[0] != stamp:
+            elem, face = pairs()
+            hit = (stamp, op.face_set(elem, face))
+            self._face_sets[key] = hit
+        return hit[1]
+
+    def boundary_face_set(self, name):
+        """The named boundary as one ``faces.FaceSet`` in the order of
+        ``Mesh.boundary_faces(name)``: its normals, ``integrate``, ``flux``
+        and the Neumann load ``assemble`` run on the device."""
+        if name not in self._mesh._boundary_id_lookup:
+            raise KeyError(name)
+        return self._face_set(("boundary", name), lambda: self._mesh.boundary_faces(name))
+
+    def _all_faces(self):
+        """Every face of every cell (row = cell * 2 ndim + face): what
+        ``FiniteElement.sub_fe`` and ``Mapping.get_submapping`` view."""
+        E, nd = self._mesh.n_cells, self._mesh.ndim
+        return self._face_set(("all",), lambda: (np.repeat(np.arange(E), 2 * nd),
+                                                 np.tile(np.arange(2 * nd), E)))
+
+    def _face_view(self, index, face):
+        return self._all_faces().host(), index * 2 * self._mesh.ndim + face
+
     def boundary_elements(self, name, **compute_flags):
-        raise NotImplementedError("boundary sub-elements (sem/discrete.py:211-219) are out of "
-                                  "scope for the operator engine")
+        """Iterate over (parent element, boundary sub-element) of the named
+        boundary (sem/discrete.py:211-219); the geometry of all its faces is
+        computed once on the device (``boundary_face_set``)."""
+        self._resolve_cmpflag_dependencies(compute_flags)
+        host = self.boundary_face_set(name).host()
+        elem, face = self._mesh.boundary_faces(name)
+        fe_parent = None
+        for k in range(elem.size):
+            i = int(elem[k])
+            if fe_parent is None or fe_parent._index != i:
+                fe_parent = FiniteElement(self, self._mesh.get_cell(i), compute_flags, i)
+            yield fe_parent, SubFiniteElement(fe_parent, int(face[k]), host, k)
 
     def values_at_nodes(self, coeffs):
         """Values at the equispaced element nodes (sem/discrete.py:235-258),
@@ -836,8 +935,10 @@ class FiniteElement(object):
         self._quad_rule = self._basis.quad_rule
         self._cmpflags = compute_flags
         self._index = index
+        self._dof_mngr = dof_mngr
         fields = dof_mngr.geometry_fields() if compute_flags.get("x_phys") else {}
-        self._mapping = Mapping(dof_mngr._map_basis, fields, index, compute_flags)
+        self._mapping = Mapping(dof_mngr._map_basis, fields, index, compute_flags,
+                                face_source=lambda face: dof_mngr._face_view(index, face))
         self._l_dof_ind_hier, self._g_dof_ind_hier = self._compute_hier_dofs()
 
     def _compute_hier_dofs(self):
@@ -949,3 +1050,115 @@ class FiniteElement(object):
 
     def values_at_nodes(self, coeffs):
         return self._basis.interpolate_on_grid_eq(coeffs)
+
+    def sub_fe(self, face):
+        """The sub-element on ``face`` (= 2 * axis + side) of this element
+        (sem/discrete.py:699-700), a view of the DOFManager's batched face
+        geometry."""
+        face = int(face)
+        if not 0 <= face < 2 * self.ndim:
+            raise ValueError("face must be in [0, %d)" % (2 * self.ndim))
+        host, row = self._dof_mngr._face_view(self._index, face)
+        return SubFiniteElement(self, face, host, row)
+
+    def boundary_elements(self, name):
+        """Sub-elements of this element on the boundary ``name``
+        (sem/discrete.py:702-705)."""
+        bnd_id = self._cell._mesh._boundary_id_lookup[name]
+        for _, face in self._cell._boundary_data.get(bnd_id, []):
+            yield self.sub_fe(face)
+
+
+class SubFiniteElement(object):
+    """Finite element on a face of a higher-dimensional one
+    (sem/discrete.py:708-775).  Its geometry is row ``row`` of the host
+    arrays of a ``faces.FaceSet``; arrays are [.., n] on a quadrilateral's
+    side and [.., n, n] on a hexahedron's face, in the face order of
+    include/sem_hip.h "Faces"."""
+
+    def __init__(self, parent_fe, face, fields, row):
+        from .mapping import SubMapping
+        self._parent_fe = parent_fe
+        self._face = face
+        self._fields = fields
+        self._row = row
+        self._dpn = parent_fe._dpn
+        self._mapping = SubMapping(parent_fe.mapping, face, fields, row)
+
+    @property
+    def parent_fe(self):
+        return self._parent_fe
+
+    @property
+    def face(self):
+        return self._face
+
+    @property
+    def ndim(self):
+        return self._parent_fe.ndim - 1
+
+    @property
+    def mapping(self):
+        return self._mapping
+
+    @property
+    def n_nodes(self):
+        return int(self._fields["dS"][self._row].size)
+
+    @property
+    def ndof(self):
+        return self.n_nodes * self._dpn
+
+    @property
+    def x_phys(self):
+        return self._mapping.x_phys
+
+    @property
+    def node_ind(self):
+        """Global node ids of the face nodes (uint32, as the parent's)."""
+        return self._fields["node_ind"][self._row].astype(np.uint32)
+
+    @property
+    def n_dS(self):
+        return self._mapping.n_dS
+
+    @property
+    def dS(self):
+        return self._mapping.dS
+
+    @property
+    def dSxW(self):
+        return self._fields["dSxW"][self._row]
+
+    @property
+    def unit_normal(self):
+        return self._mapping.unit_normal
+
+    @property
+    def n_dSxW(self):
+        return self.unit_normal * self.dSxW
+
+    def slice_from_parent(self, arr):
+        from .faces import subface_slice
+        return subface_slice(self._face, arr, self._parent_fe.ndim)
+
+    def parent_dofs(self):
+        """Parent-local DOF numbers of the face DOFs (sem/discrete.py:757-766)."""
+        from .faces import face_index_table
+        nd = self._parent_fe.ndim
+        n = self._fields["dS"].shape[-1]
+        node_idx = face_index_table(nd, n)[self._face].astype(np.uint32)
+        dpn = np.uint32(self._dpn)
+        return (node_idx[:, None] * dpn + np.arange(dpn, dtype=np.uint32)).ravel()
+
+    def integrate(self, coeffs):
+        """sum coeffs dSxW over the face nodes (sem/discrete.py:768-769)."""
+        axes = tuple(range(-self.ndim, 0))
+        return (np.asarray(coeffs) * self.dSxW).sum(axis=axes)
+
+    def gradient(self, coeffs):
+        """Physical gradient of the parent's local coefficients [.., n, n(, n)]
+        at the face nodes (sem/discrete.py:771-774): the parametric gradient
+        sliced to the face, times the face's invJ."""
+        g = np.asarray(self._parent_fe.basis.gradient(np.asarray(coeffs, dtype=np.float64)))
+        return np.einsum("ij...,i...->j...", self._mapping.invJ, self.slice_from_parent(g))

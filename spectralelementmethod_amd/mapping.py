@@ -10,8 +10,9 @@ k_geometry in csrc/sem_kernels.h) and a ``Mapping`` is a view of cell i.
 device is needed.  Locating many points over the whole mesh is the device
 path of ``points.PointLocator``.
 
-Out of scope: face ``SubMapping``s (boundary-condition
-surface terms); they raise NotImplementedError.
+``Mapping.get_submapping(face)`` returns a ``SubMapping`` (sem/mapping.py:
+184-272): a view of one face of the batched ``faces.FaceSet`` the DOFManager
+keeps for all faces of all cells.
 """
 import numpy as np
 
@@ -23,11 +24,13 @@ class OutsideDomain(Exception):
 
 
 class Mapping(object):
-    def __init__(self, basis, fields, index, compute_flags):
+    def __init__(self, basis, fields, index, compute_flags, face_source=None):
         self._basis = basis
         self._fields = fields
         self._i = index
         self._cmpflags = dict(compute_flags)
+        # face -> (host arrays of a FaceSet, row) of this cell's face
+        self._face_source = face_source
 
     @property
     def ndim(self):
@@ -95,4 +98,45 @@ class Mapping(object):
                             "finite element.")
 
     def get_submapping(self, face):
-        raise NotImplementedError("face sub-mappings (sem/mapping.py:184-272) are out of scope")
+        """The mapping of one face (sem/mapping.py:180-181), a view of the
+        DOFManager's batched face geometry."""
+        if self._face_source is None:
+            raise ValueError("this Mapping belongs to no DOFManager: no face geometry")
+        face = int(face)
+        if not 0 <= face < 2 * self.ndim:
+            raise ValueError("face must be in [0, %d)" % (2 * self.ndim))
+        fields, row = self._face_source(face)
+        return SubMapping(self, face, fields, row)
+
+
+class SubMapping(object):
+    """One face of an element (sem/mapping.py:184-272): ``x_phys``, ``J``,
+    ``invJ``, ``detJ`` of the parent at the face nodes and the scaled normal
+    ``n_dS`` with ``dS`` and ``unit_normal``, in the face order of
+    include/sem_hip.h "Faces".  Views of row ``row`` of a ``faces.FaceSet``'s
+    host arrays; 3-D faces have the normal the reference leaves unfinished."""
+
+    def __init__(self, parent_mapping, face, fields, row):
+        self._parent_mapping = parent_mapping
+        self._face = face
+        self._fields = fields
+        self._row = row
+
+    @property
+    def ndim(self):
+        return self._parent_mapping.ndim - 1
+
+    def _get(self, key):
+        return self._fields[key][self._row]
+
+    x_phys = property(lambda self: self._get("x_phys"))
+    J = property(lambda self: self._get("J"))
+    invJ = property(lambda self: self._get("invJ"))
+    detJ = property(lambda self: self._get("detJ"))
+    n_dS = property(lambda self: self._get("n_dS"))
+    dS = property(lambda self: self._get("dS"))
+    unit_normal = property(lambda self: self._get("unit_normal"))
+
+    def inv(self, x_phys):
+        raise NotImplementedError("Cannot compute the parametric coordinates of a SubMapping "
+                                  "from physical coordinates.")

@@ -357,6 +357,13 @@ class SEMOperator(object):
             self._locator = PointLocator(self)
         return self._locator
 
+    def face_set(self, elem, face):
+        """The ``faces.FaceSet`` of the given (element, face) pairs of this
+        operator's mesh: normals, surface integrals and Neumann loads on the
+        device (face = 2 * axis + side, include/sem_hip.h "Faces")."""
+        from .faces import FaceSet
+        return FaceSet(self, elem, face)
+
     # ------------------------------------------------------------------
     def _vec(self, v, name):
         if not isinstance(v, torch.Tensor):
