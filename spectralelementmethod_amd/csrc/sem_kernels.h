@@ -1,4 +1,5 @@
-// Device kernels of libsem_hip.so (included once, by sem_device.hip).
+// Device kernels of libsem_hip.so (included, through sem_ctx.h, by every
+// device unit of the library).
 //
 // Hot path (BASELINE.json north_star):
 //   for every element e:  u_e = u[map[e]]                       (gather)
@@ -52,28 +53,14 @@ struct ChainWaves {
 };
 constexpr int MAXN = 17;
 
-#ifndef SEM_POISSON_MIN_WAVES
-#define SEM_POISSON_MIN_WAVES 0  // 0: per-order choice (PoissonMinWaves)
-#endif
-#ifndef SEM_NT_MAP
-#define SEM_NT_MAP 0  // map stream read with nontemporal loads
-#endif
-#ifndef SEM_NT_STORE
-#define SEM_NT_STORE 1  // first-writer y stores nontemporal
-#endif
-#ifndef SEM_RMW_PREFETCH
-#define SEM_RMW_PREFETCH 1  // Poisson: read read-modify-write targets before the last passes
-#endif
+// Poisson: the read-modify-write targets are read before the last passes.
 // The prefetch holds n operands per lane through the last contractions:
 // measured on MI355X at ~1e7 DOF it pays up to n = 13 (p = 12: 0.142 vs
 // 0.163 ms) and costs at n = 17 (p = 16: 0.197 vs 0.176 ms; 246 vs 159
 // VGPRs, profiles/r02/variants).
-#ifndef SEM_RMW_PREFETCH_17
-#define SEM_RMW_PREFETCH_17 0  // n = 17: 0 off, 1 / 2 as SEM_RMW_PREFETCH
-#endif
 template <int N>
 struct RmwPrefetch {
-  static constexpr int value = N <= 16 ? SEM_RMW_PREFETCH : SEM_RMW_PREFETCH_17;
+  static constexpr bool value = N <= 16;
 };
 
 // D1 in even-odd form.  D is centro-antisymmetric (D[N-1-i][N-1-j] =
@@ -91,14 +78,11 @@ struct RmwPrefetch {
 #ifndef SEM_D_SCALAR_LOAD_N
 #define SEM_D_SCALAR_LOAD_N 10
 #endif
-#ifndef SEM_DEO_TRANSPOSED
-#define SEM_DEO_TRANSPOSED 1
-#endif
 template <int N>
 struct DEOData {
   static constexpr int H = N / 2;
   static constexpr int C = N % 2;
-  static constexpr bool TR = SEM_DEO_TRANSPOSED && N >= SEM_D_SCALAR_LOAD_N;
+  static constexpr bool TR = N >= SEM_D_SCALAR_LOAD_N;
   double P[H * H];
   double Q[H * H];
   double cc[C ? H : 1];
@@ -155,11 +139,6 @@ template <int N>
 struct DEOConstData {
   static constexpr bool available = false;
 };
-// SEM_CONST_D_PIN: each constant is materialised at its use (an empty asm on
-// its SGPR pair), never hoisted out of the round loop
-#ifndef SEM_CONST_D_PIN
-#define SEM_CONST_D_PIN 0
-#endif
 }  // namespace semk
 #include "deo_const.h"
 namespace semk {
@@ -308,20 +287,12 @@ __device__ __forceinline__ void deo_const_apply(const double (&x)[N], Store&& st
     constexpr int m = decltype(mI)::value;
     double sp = 0.0, tp = 0.0;
     if constexpr (N % 2) {
-      double c = TR ? K::rr[m] : K::cc[m];
-      if constexpr (SEM_CONST_D_PIN) asm volatile("" : "+s"(c));
-      tp = c * x[H];
+      tp = (TR ? K::rr[m] : K::cc[m]) * x[H];
     }
     sfor<H>([&](auto rI) {
       constexpr int r = decltype(rI)::value;
-      double a = TR ? K::Q[r * H + m] : K::P[m * H + r];
-      double b = TR ? K::P[r * H + m] : K::Q[m * H + r];
-      if constexpr (SEM_CONST_D_PIN) {  // materialised here, never hoisted
-        asm volatile("" : "+s"(a));
-        asm volatile("" : "+s"(b));
-      }
-      sp = fma(a, o[r], sp);
-      tp = fma(b, e[r], tp);
+      sp = fma(TR ? K::Q[r * H + m] : K::P[m * H + r], o[r], sp);
+      tp = fma(TR ? K::P[r * H + m] : K::Q[m * H + r], e[r], tp);
     });
     st(m, sp + tp);
     st(N - 1 - m, sp - tp);
@@ -330,9 +301,7 @@ __device__ __forceinline__ void deo_const_apply(const double (&x)[N], Store&& st
     double a = 0.0;
     sfor<H>([&](auto rI) {
       constexpr int r = decltype(rI)::value;
-      double c = TR ? K::cc[r] : K::rr[r];
-      if constexpr (SEM_CONST_D_PIN) asm volatile("" : "+s"(c));
-      a = fma(c, o[r], a);
+      a = fma(TR ? K::cc[r] : K::rr[r], o[r], a);
     });
     st(H, a);
   }
@@ -388,7 +357,7 @@ __device__ __forceinline__ double rmw_load(const double* p) { return __builtin_n
 // NT: nontemporal first-writer stores (the column kernels' row-contiguous
 // scatter; the MFMA kernel's scattered 16 x 16 layout measured 10 % slower
 // with them at p = 12)
-template <bool NT = (SEM_NT_STORE != 0)>
+template <bool NT = true>
 __device__ __forceinline__ void emit1(double* __restrict__ y, uint32_t raw, double v,
                                       int accumulate) {
   const uint32_t a = (raw >> CODE_SHIFT) & 3u;
@@ -440,11 +409,7 @@ __device__ __forceinline__ void emit1p(double* __restrict__ y, uint32_t raw, dou
   const uint32_t a = (raw >> CODE_SHIFT) & 3u;
   double* dst = y + (raw & GID_MASK);
   if (a == W_STORE || a == W_RMW) {  // prev = 0 for a first writer in overwrite mode
-#if SEM_NT_STORE
-      __builtin_nontemporal_store(prev + v, dst);
-#else
-      *dst = prev + v;
-#endif
+    __builtin_nontemporal_store(prev + v, dst);
   } else if (a == W_ATOMIC) {
     atomic_add_f64(dst, v);
   }
@@ -474,15 +439,9 @@ struct NoPrefetch {
 struct SeamOut {
   double* base = nullptr;  // buf + colour * n_node * dpn of the chain
 };
-#ifndef SEM_NT_STORE_SEAM
-#define SEM_NT_STORE_SEAM 1  // the seam plan's y and slot stores nontemporal
-#endif
-template <bool NT = (SEM_NT_STORE_SEAM != 0)>
+// the seam plan's y and slot stores are nontemporal
 __device__ __forceinline__ void st_seam(double v, double* dst) {
-  if constexpr (NT)
-    __builtin_nontemporal_store(v, dst);
-  else
-    *dst = v;
+  __builtin_nontemporal_store(v, dst);
 }
 __device__ __forceinline__ void emit1_seam(double* __restrict__ y, uint32_t raw, double v,
                                            int accumulate, const SeamOut& so) {
@@ -512,24 +471,18 @@ __device__ __forceinline__ void emit2(double* __restrict__ y, uint32_t raw, doub
   }
 }
 
-// SEM_LDS_SPLIT: tile loads of the nodal kernel as single 8-byte LDS reads.
+// SPLIT: tile loads of the nodal kernel as single 8-byte LDS reads.
 // The compiler pairs neighbouring reads into ds_read2_b64, which the MI355X
 // LDS serves at half the rate of two ds_read_b64 (MI355X_MICROARCH.md §LDS:
 // 8 cycles against 2 x 2); a volatile access is never paired (and keeps the
 // LDS address space: a generic volatile pointer became flat loads and
 // spilled).  p = 8 at 1024^2, alternating on one box: 0.6726-0.6803 against
 // 0.6827-0.6882 ms per step (profiles/r03/lds_split/).
-#ifndef SEM_LDS_SPLIT
-#define SEM_LDS_SPLIT 1
-#endif
 // the same for the column reads of the stored-factor kernel, from order
 // SEM_LDS_SPLIT_STORED_N (profiles/r03/lds_split/stored/: p = 16 0.141-0.146
 // -> 0.138-0.139 ms, but p = 6 0.126 -> 0.134 and p = 12 neutral)
 #ifndef SEM_LDS_SPLIT_STORED_N
 #define SEM_LDS_SPLIT_STORED_N 17
-#endif
-#ifndef SEM_LDS_SPLIT_AXI  // and of the fields-first axisymmetric nodal kernel
-#define SEM_LDS_SPLIT_AXI 0
 #endif
 template <bool SPLIT>
 __device__ __forceinline__ double lds_ld(const double* p) {
@@ -539,31 +492,27 @@ __device__ __forceinline__ double lds_ld(const double* p) {
     return *p;
 }
 
-// row i of the tile (RL doubles at row stride RS; 16-B aligned loads when
-// both are even) -> registers
-template <int N, int RS, int RL = RS, bool SPLIT = false>
-__device__ __forceinline__ void load_row(const double* L, int i, double (&r)[RL]) {
-  if constexpr (RL % 2 == 0 && RS % 2 == 0) {
+// row i of the tile (RS doubles; 16-B aligned loads when RS is even) ->
+// registers
+template <int N, int RS, bool SPLIT = false>
+__device__ __forceinline__ void load_row(const double* L, int i, double (&r)[RS]) {
+  if constexpr (RS % 2 == 0) {
     const double2* row = reinterpret_cast<const double2*>(L + i * RS);
 #pragma unroll
-    for (int s = 0; s < RL / 2; ++s) {
+    for (int s = 0; s < RS / 2; ++s) {
       const double2 v = row[s];
       r[2 * s] = v.x;
       r[2 * s + 1] = v.y;
     }
   } else {
 #pragma unroll
-    for (int s = 0; s < RL; ++s) r[s] = lds_ld<SPLIT>(L + i * RS + s);
+    for (int s = 0; s < RS; ++s) r[s] = lds_ld<SPLIT>(L + i * RS + s);
   }
 }
 
-// ACTIVE false: the lane stores at L + JUNK instead of its row (padding
-// lanes of the wave-linear tile, whose row would run into the next tile row;
-// an address select, not a branch: a masked store region spilled registers)
-template <int N, int RS, int JUNK = 0>
-__device__ __forceinline__ void store_row(double* L, int i, const double (&t)[N],
-                                          bool active = true) {
-  double* row = L + (active ? i * RS : JUNK);
+template <int N, int RS>
+__device__ __forceinline__ void store_row(double* L, int i, const double (&t)[N]) {
+  double* row = L + i * RS;
   if constexpr (RS % 2 == 0) {
     double2* row2 = reinterpret_cast<double2*>(row);
 #pragma unroll
@@ -582,19 +531,12 @@ __device__ __forceinline__ void store_row(double* L, int i, const double (&t)[N]
 // vs unpadded: 0.704 vs 0.720 ms (nodal).  At N = 9, slot stride 90 doubles
 // and row stride 10 keep column and row accesses within 1.5x of conflict-free
 // (bank model of MI355X_MICROARCH.md §LDS).
-#ifndef SEM_TILE_PAD_STORED
-#define SEM_TILE_PAD_STORED 1
-#endif
-// per order: p = 14 (n = 15) unpadded, 0.1209-0.1211 against 0.1234-0.1248
-// ms per action (profiles/r04/knobs_high/, call P; p = 12 / 16 unchanged);
-// p = 10 (n = 11) unpadded 0.1075-0.1085 against 0.1091-0.1094 (call S)
-constexpr bool stored_pad(int n) { return SEM_TILE_PAD_STORED && n != 15 && n != 11; }
-#ifndef SEM_TILE_PAD_NODAL
-#define SEM_TILE_PAD_NODAL 0
-#endif
-#ifndef SEM_NODAL_EARLY_U
-#define SEM_NODAL_EARLY_U 0
-#endif
+// The stored-factor kernel's tiles are padded, per order: p = 14 (n = 15)
+// unpadded, 0.1209-0.1211 against 0.1234-0.1248 ms per action
+// (profiles/r04/knobs_high/, call P; p = 12 / 16 unchanged); p = 10 (n = 11)
+// unpadded 0.1075-0.1085 against 0.1091-0.1094 (call S).  The nodal Poisson
+// kernel's two tile planes are unpadded (they fit 4 workgroups per CU).
+constexpr bool stored_pad(int n) { return n != 15 && n != 11; }
 template <int N, bool PAD = true>
 struct Tile {
   static constexpr int EPW = WAVE / N;
@@ -608,59 +550,17 @@ struct Tile {
   }
 };
 
-// Wave-linear tiles (nodal Poisson kernel): the wave's EPW element tiles
-// side by side, element k at column offset k*N of one N x WL_RS array,
-//   T[k][r][c] at  wave base + r*WL_RS + k*N + c,   WL_RS = 65 (= 1 mod 32).
-// A column access (fixed r) is the wave's lanes in order, a row access
-// (lane (k, j) reads row j) is lane + 64 j + c: both free of bank conflicts
-// for 64-bit LDS accesses (MI355X_MICROARCH.md §LDS), where the element-slot
-// layout (slot stride N*N) has 2-way conflicts on every column access.  The
-// padding lanes' columns are the spare columns LW..64 of each row; their
-// row stores go to a junk row after the wave's N rows (theirs would run into
-// the next tile row).
-#ifndef SEM_TILE_WL
-#define SEM_TILE_WL 0
-#endif
-constexpr int WL_RS = 65;
-template <int N>
-struct WLTile {
-  static constexpr int RS = WL_RS;
-  static constexpr int LW = (WAVE / N) * N;
-  static constexpr int WS = N * WL_RS + N;  // doubles per wave: N rows + the junk row
-  static constexpr int JUNK = N * WL_RS - LW;  // junk row, from a padding lane's base
-  __device__ static int base(int wave, int k) { return wave * WS + k * N; }
-};
-
-
-
 // Row pass on a wave-private tile: the lane's row j (written column-wise by
 // the wave and synchronised) is contracted with D (or D^T when TR) and
 // written back, so the tile again holds the result in column layout.  REL
 // differentiates relative to the row's first entry (see poisson_group_nodal).
-// RL: doubles loaded per row (RS, or N on the wave-linear tile); ACTIVE:
-// whether the lane stores its row.
 #ifndef SEM_ROW_STORE_PAIRS_N
 #define SEM_ROW_STORE_PAIRS_N 17  // orders from which row passes store output pairs directly
 #endif
-// the stored-factor kernel's tile: wave-linear from order
-// SEM_TILE_WL_STORED_N (conflict-free column and row accesses, §4.6; rows
-// of 8-byte reads instead of 16-byte pairs), below the orders whose row
-// passes store output pairs directly (their padding lanes have no junk row)
-#ifndef SEM_TILE_WL_STORED_N
-#define SEM_TILE_WL_STORED_N 99
-#endif
-template <int N>
-struct StoredTile {
-  static constexpr bool wl = N >= SEM_TILE_WL_STORED_N && N < SEM_ROW_STORE_PAIRS_N;
-  static constexpr int RS = wl ? WL_RS : Tile<N, stored_pad(N)>::RS;
-  static constexpr int RL = wl ? N : RS;  // doubles loaded per row
-  static constexpr int JUNK = wl ? WLTile<N>::JUNK : 0;
-};
-template <int N, int RS, bool TR, bool REL, int RL = RS, int JUNK = 0, bool SPLIT = false,
-          class DT = DEO<N>>
-__device__ __forceinline__ void row_pass(double* L, int j, const DT& D, bool active = true) {
-  double r[RL], x[N];
-  load_row<N, RS, RL, SPLIT>(L, j, r);
+template <int N, int RS, bool TR, bool REL, bool SPLIT = false, class DT = DEO<N>>
+__device__ __forceinline__ void row_pass(double* L, int j, const DT& D) {
+  double r[RS], x[N];
+  load_row<N, RS, SPLIT>(L, j, r);
 #pragma unroll
   for (int q = 0; q < N; ++q) x[q] = REL ? r[q] - r[0] : r[q];
   if constexpr (N >= SEM_ROW_STORE_PAIRS_N) {
@@ -674,7 +574,7 @@ __device__ __forceinline__ void row_pass(double* L, int j, const DT& D, bool act
     else
       deo_apply<N>(D, x, t);
     wave_sync();
-    store_row<N, RS, JUNK>(L, j, t, active);
+    store_row<N, RS>(L, j, t);
   }
   wave_sync();
 }
@@ -758,41 +658,9 @@ __device__ __forceinline__ void load_map(const MapRef& m, int64_t g, int lane, b
     const uint32_t* mp = m.p32 + g * (int64_t)(N * LW) + lane;
 #pragma unroll
     for (int r = 0; r < N; ++r)
-#if SEM_NT_MAP
-      raw[r] = in_wave ? __builtin_nontemporal_load(mp + r * LW) : (W_SKIP << CODE_SHIFT);
-#else
       raw[r] = in_wave ? mp[r * LW] : (W_SKIP << CODE_SHIFT);
-#endif
   }
 }
-
-// Next-round map prefetch into the caches (SEM_MAP_TOUCH, column kernel with
-// the 16-bit map): the 16-bit entries of group g (N * LW * 2 bytes) and its
-// N bases, read as dwords by the wave's lanes -- no registers are held for
-// the data, only the loaded dwords until MapTouch::done, which an empty asm
-// consumes at the end of the round (a load whose value is unused would be
-// dropped; consuming it earlier would wait for it).  The next round's
-// load_map then finds its lines in L2.  (Default 0: sem_plan.h.)
-template <int N>
-struct MapTouch {
-  static constexpr int LW = Tile<N>::LW;
-  static constexpr int DW = (N * LW * 2 + 3) / 4;  // dwords of 16-bit entries
-  static constexpr int K = (DW + WAVE - 1) / WAVE;
-  uint32_t t[K + 1];
-  __device__ __forceinline__ void issue(const MapRef& m, int64_t g, int lane) {
-    const uint32_t* p = reinterpret_cast<const uint32_t*>(m.p16 + g * (int64_t)(N * LW));
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-      const int d = k * WAVE + lane;
-      t[k] = p[d < DW ? d : DW - 1];
-    }
-    t[K] = m.base[g * N + (lane < N ? lane : N - 1)];
-  }
-  __device__ __forceinline__ void done() {
-#pragma unroll
-    for (int k = 0; k <= K; ++k) asm volatile("" ::"v"(t[k]));
-  }
-};
 
 // ---------------------------------------------------------------------------
 // One group of the Poisson action with STORED factors: returns y_e[p][j]
@@ -811,10 +679,7 @@ __device__ __forceinline__ void poisson_group_stored(const MapRef& mref,
                                                      const Pre& pre = Pre()) {
   using T = Tile<N, stored_pad(N)>;
   constexpr int LW = T::LW;
-  constexpr int RS = StoredTile<N>::RS;
-  constexpr int RL = StoredTile<N>::RL;
-  constexpr int JUNK = StoredTile<N>::JUNK;
-  const bool act = in_wave || !StoredTile<N>::wl;
+  constexpr int RS = T::RS;
   constexpr bool SP = N >= SEM_LDS_SPLIT_STORED_N;
   const double* gp = GP + g * (int64_t)(3 * N * LW) + lane;
   double uc[N];
@@ -830,7 +695,7 @@ __device__ __forceinline__ void poisson_group_stored(const MapRef& mref,
   for (int r = 0; r < N; ++r) L[r * RS + j] = uc[r];
   wave_sync();
   // row i = j: d1[i][q] = sum_s D[q][s] u[i][s]     (TensorProduct.deriv dim 1)
-  row_pass<N, RS, false, false, RL, JUNK>(L, j, D, act);
+  row_pass<N, RS, false, false>(L, j, D);
   // column j: w0/w1, and ya = D^T w0 along xi0 (kept in v); w1 -> tile
   {
     double w0[N];
@@ -843,15 +708,15 @@ __device__ __forceinline__ void poisson_group_stored(const MapRef& mref,
       w0[m] = fma(g00, d0[m], g01 * d1);
       L[m * RS + j] = fma(g01, d0[m], g11 * d1);  // w1, same lane's slot
     }
-    constexpr int PF = Pre::prefetch ? RmwPrefetch<N>::value : 0;
-    if constexpr (PF) pre();
-    if constexpr (PF == 1) rmw_prefetch<N, Pre::aux>(y, raw, accumulate, prev);
+    if constexpr (Pre::prefetch && RmwPrefetch<N>::value) {
+      pre();
+      rmw_prefetch<N, Pre::aux>(y, raw, accumulate, prev);
+    }
     deo_apply_t<N>(D, w0, v);
-    if constexpr (PF == 2) rmw_prefetch<N, Pre::aux>(y, raw, accumulate, prev);
   }
   wave_sync();
   // row i = j: yb[i][q] = sum_n D[n][q] w1[i][n]
-  row_pass<N, RS, true, false, RL, JUNK>(L, j, D, act);
+  row_pass<N, RS, true, false>(L, j, D);
 #pragma unroll
   for (int p = 0; p < N; ++p) v[p] += lds_ld<SP>(L + p * RS + j);
   wave_sync();  // the tile is rewritten by the next group of this wave
@@ -903,45 +768,22 @@ __device__ __forceinline__ void gather_u(const double* __restrict__ u, const uin
   }
 }
 
+// the nodal kernel's tile: unpadded element slots, read with split loads
+template <int N>
+struct NodalTile {
+  static constexpr int RS = Tile<N, false>::RS;
+  static constexpr bool split = true;
+};
+
 // geometry of the group from its node coordinates: (dx/dr, dy/dr) along the
 // column, (dx/ds, dy/ds) along the row -> G00, G01 in registers, G11 parked
 // in tile B (free until the next group) to save registers
-// the nodal kernel's tile: wave-linear (SEM_TILE_WL) below the orders whose
-// row passes store pairs directly (unmasked), element slots otherwise
-template <int N>
-struct NodalTile {
-  static constexpr bool wl = SEM_TILE_WL && N < SEM_ROW_STORE_PAIRS_N;
-  static constexpr int RS = wl ? WL_RS : Tile<N, SEM_TILE_PAD_NODAL>::RS;
-  static constexpr int RL = wl ? N : RS;  // doubles loaded per row
-  static constexpr int JUNK = wl ? WLTile<N>::JUNK : 0;
-  static constexpr bool split = SEM_LDS_SPLIT;
-};
 
-// SEM_W_SCALAR_LOAD: the nodal geometry reads w_m with scalar loads from the
-// device copy once per round (pointer laundered, so neither hoisted nor kept)
-// instead of holding the 2n SGPRs of the kernel argument for the whole launch
-#ifndef SEM_W_SCALAR_LOAD
-#define SEM_W_SCALAR_LOAD 0
-#endif
-using CWPtr = const __attribute__((address_space(4))) double*;
-__device__ __forceinline__ CWPtr wrow(const double* wp) {
-  CWPtr q = (CWPtr)wp;
-  if constexpr (SEM_W_SCALAR_LOAD) asm volatile("" : "+s"(q));
-  return q;
-}
-template <int N>
-__device__ __forceinline__ double wsel(const WVec<N>& w, CWPtr q, int m) {
-  if constexpr (SEM_W_SCALAR_LOAD)
-    return q[m];
-  else
-    return w.v[m];
-}
 template <int N, class DT>
 __device__ __forceinline__ void nodal_geometry(const double2 (&xc)[N], int j, double* A, double* B,
                                                const DT& D, const WVec<N>& w, double wj,
-                                               double (&g00)[N], double (&g01)[N], bool in_wave, const double* wp = nullptr) {
+                                               double (&g00)[N], double (&g01)[N]) {
   constexpr int RS = NodalTile<N>::RS;
-  constexpr int RL = NodalTile<N>::RL;
   double jr0[N], jr1[N];
   {
     double ta[N], tb[N];
@@ -960,9 +802,9 @@ __device__ __forceinline__ void nodal_geometry(const double2 (&xc)[N], int j, do
   }
   wave_sync();
   {
-    double xa[RL], xb[RL], ra[N], rb[N], ta[N], tb[N];
-    load_row<N, RS, RL, NodalTile<N>::split>(A, j, xa);
-    load_row<N, RS, RL, NodalTile<N>::split>(B, j, xb);
+    double xa[RS], xb[RS], ra[N], rb[N], ta[N], tb[N];
+    load_row<N, RS, NodalTile<N>::split>(A, j, xa);
+    load_row<N, RS, NodalTile<N>::split>(B, j, xb);
 #pragma unroll
     for (int q = 0; q < N; ++q) {
       ra[q] = xa[q] - xa[0];
@@ -971,11 +813,10 @@ __device__ __forceinline__ void nodal_geometry(const double2 (&xc)[N], int j, do
     deo_apply<N>(D, ra, ta);
     deo_apply<N>(D, rb, tb);
     wave_sync();
-    store_row<N, RS, NodalTile<N>::JUNK>(A, j, ta, in_wave || !NodalTile<N>::wl);
-    store_row<N, RS, NodalTile<N>::JUNK>(B, j, tb, in_wave || !NodalTile<N>::wl);
+    store_row<N, RS>(A, j, ta);
+    store_row<N, RS>(B, j, tb);
   }
   wave_sync();
-  const auto wq = wrow(wp);
 #pragma unroll
   for (int m = 0; m < N; ++m) {
     constexpr bool SP = NodalTile<N>::split;
@@ -983,7 +824,7 @@ __device__ __forceinline__ void nodal_geometry(const double2 (&xc)[N], int j, do
     const double det = jr0[m] * js1 - js0 * jr1[m];
     // (w_m w_j) / det, associated so that no loop-invariant w_m w_j array
     // is hoisted out of the round loop (9 doubles spilled at 4 waves/SIMD)
-    const double sc = wsel<N>(w, wq, m) * (wj * fast_rcp(det));
+    const double sc = w.v[m] * (wj * fast_rcp(det));
     g00[m] = sc * fma(js1, js1, js0 * js0);
     g01[m] = -sc * fma(js1, jr1[m], js0 * jr0[m]);
     B[m * RS + j] = sc * fma(jr1[m], jr1[m], jr0[m] * jr0[m]);  // G11, own slot
@@ -998,18 +839,15 @@ __device__ __forceinline__ void nodal_laplacian(const double (&uc)[N], int j, do
                                                 const double (&g00)[N], const double (&g01)[N],
                                                 double (&v)[N], const double* __restrict__ y,
                                                 const uint32_t (&raw)[N], int accumulate,
-                                                double (&prev)[N], bool in_wave,
-                                                const Pre& pre = Pre()) {
+                                                double (&prev)[N], const Pre& pre = Pre()) {
   constexpr int RS = NodalTile<N>::RS;
-  constexpr int RL = NodalTile<N>::RL;
-  const bool act = in_wave || !NodalTile<N>::wl;
   double d0[N];
   deo_apply<N>(D, uc, d0);
 #pragma unroll
   for (int r = 0; r < N; ++r) A[r * RS + j] = uc[r];
   wave_sync();
   constexpr bool SP = NodalTile<N>::split;
-  row_pass<N, RS, false, false, RL, NodalTile<N>::JUNK, SP>(A, j, D, act);
+  row_pass<N, RS, false, false, SP>(A, j, D);
   {
     double w0[N];
 #pragma unroll
@@ -1018,14 +856,14 @@ __device__ __forceinline__ void nodal_laplacian(const double (&uc)[N], int j, do
       w0[m] = fma(g00[m], d0[m], g01[m] * d1);
       A[m * RS + j] = fma(g01[m], d0[m], lds_ld<SP>(B + m * RS + j) * d1);
     }
-    constexpr int PF = Pre::prefetch ? RmwPrefetch<N>::value : 0;
-    if constexpr (PF) pre();
-    if constexpr (PF == 1) rmw_prefetch<N, Pre::aux>(y, raw, accumulate, prev);
+    if constexpr (Pre::prefetch && RmwPrefetch<N>::value) {
+      pre();
+      rmw_prefetch<N, Pre::aux>(y, raw, accumulate, prev);
+    }
     deo_apply_t<N>(D, w0, v);
-    if constexpr (PF == 2) rmw_prefetch<N, Pre::aux>(y, raw, accumulate, prev);
   }
   wave_sync();
-  row_pass<N, RS, true, false, RL, NodalTile<N>::JUNK, SP>(A, j, D, act);
+  row_pass<N, RS, true, false, SP>(A, j, D);
 #pragma unroll
   for (int p = 0; p < N; ++p) v[p] += lds_ld<SP>(A + p * RS + j);
   wave_sync();  // the tiles are rewritten by the next group of this wave
@@ -1042,33 +880,25 @@ __device__ __forceinline__ void poisson_group_nodal(const MapRef& mref,
                                                     const WVec<N>& w, double wj,
                                                     uint32_t (&raw)[N], double (&v)[N],
                                                     const double* __restrict__ y, int accumulate,
-                                                    double (&prev)[N], const Pre& pre = Pre(), const double* wp = nullptr) {
+                                                    double (&prev)[N], const Pre& pre = Pre()) {
   double uc[N];
   double2 xc[N];
   load_map<N, M16, LD, PAT>(mref, g, lane, in_wave, raw);
   gather_x<N>(XG, raw, j, xc);
-#if SEM_NODAL_EARLY_U
-  gather_u<N>(u, raw, uc);
-#endif
   double g00[N], g01[N];
-  nodal_geometry<N>(xc, j, A, B, D, w, wj, g00, g01, in_wave, wp);
-#if !SEM_NODAL_EARLY_U
+  nodal_geometry<N>(xc, j, A, B, D, w, wj, g00, g01);
   gather_u<N>(u, raw, uc);
-#endif
-  nodal_laplacian<N>(uc, j, A, B, D, g00, g01, v, y, raw, accumulate, prev, in_wave, pre);
+  nodal_laplacian<N>(uc, j, A, B, D, g00, g01, v, y, raw, accumulate, prev, pre);
 }
 
 
-// the value of lane + 1 (lane 63: its own).  SEM_DPP_SHIFT: a DPP
-// wave_shl:1 move per dword (two VALU moves) instead of __shfl_down, whose
-// ds_bpermute goes through the LDS and waits on it.  Below n = 17 only: at
-// p = 16 the DPP form lifts the stored seam kernel to 169 VGPRs (2 waves per
-// SIMD), and holding it at 3 waves with a launch bound changed its code for
-// the worse -- 0.134 ms per action with __shfl_down against 0.152 (DPP,
-// 3-wave bound) and 0.157 (DPP), profiles/r03/p16_regression/.
-#ifndef SEM_DPP_SHIFT
-#define SEM_DPP_SHIFT 1
-#endif
+// the value of lane + 1 (lane 63: its own): a DPP wave_shl:1 move per dword
+// (two VALU moves) instead of __shfl_down, whose ds_bpermute goes through
+// the LDS and waits on it.  Below n = 17 only: at p = 16 the DPP form lifts
+// the stored seam kernel to 169 VGPRs (2 waves per SIMD), and holding it at
+// 3 waves with a launch bound changed its code for the worse -- 0.134 ms per
+// action with __shfl_down against 0.152 (DPP, 3-wave bound) and 0.157 (DPP),
+// profiles/r03/p16_regression/.
 #ifndef SEM_DPP_SHIFT_MAX_N
 #define SEM_DPP_SHIFT_MAX_N 17
 #endif
@@ -1077,7 +907,7 @@ __device__ __forceinline__ void poisson_group_nodal(const MapRef& mref,
 // against 0.1225-0.1253 ms per action, profiles/r04/knobs_high/u_*)
 template <int N, bool DPP17 = false>
 __device__ __forceinline__ double lane_next(double x) {
-  if constexpr (SEM_DPP_SHIFT && (N < SEM_DPP_SHIFT_MAX_N || DPP17)) {
+  if constexpr (N < SEM_DPP_SHIFT_MAX_N || DPP17) {
     constexpr int WAVE_SHL1 = 0x130;
     const int lo = __double2loint(x), hi = __double2hiint(x);
     return __hiloint2double(__builtin_amdgcn_update_dpp(hi, hi, WAVE_SHL1, 0xF, 0xF, false),
@@ -1087,13 +917,7 @@ __device__ __forceinline__ double lane_next(double x) {
   }
 }
 
-#ifndef SEM_ROUND_SYNC_ALWAYS
-#define SEM_ROUND_SYNC_ALWAYS 0
-#endif
 constexpr int CARRY_BUFS = 3;
-#ifndef SEM_LANE_RECOMPUTE
-#define SEM_LANE_RECOMPUTE 0
-#endif
 
 // Scatter of one group's column values through the coded map, with the
 // in-group merge (next lane) and the chain carry (previous group) applied.
@@ -1138,10 +962,6 @@ __device__ __forceinline__ void chain_emit(double* __restrict__ y, const uint32_
       if ((raw[p] >> CODE_SHIFT) & W_MERGE) v[c][p] += vn;
     }
   // hand the last lane's column to the next group of the chain
-  // SEM_LANE_RECOMPUTE: the lane tests are re-evaluated every round (the
-  // lane id laundered) instead of kept as loop-invariant SGPR masks, which
-  // the allocator spills to VGPR lanes at the register limit
-  if constexpr (SEM_LANE_RECOMPUTE) asm volatile("" : "+v"(lane));
   if (lane == LW - 1) {
 #pragma unroll
     for (int c = 0; c < NC; ++c)
@@ -1184,31 +1004,7 @@ __device__ __forceinline__ void chain_emit(double* __restrict__ y, const uint32_
   // rounds need it (SeamPlan::round_sync); the carry slots need no second
   // barrier with three buffers (a slot is rewritten three rounds later,
   // after its reader has passed the next round's first barrier)
-  if (SEM_ROUND_SYNC_ALWAYS || round_sync) __syncthreads();
-}
-
-// Workgroups are dealt round-robin over the 8 XCDs (blocks b and b + 8 share
-// one L2).  With SEM_XCD_SWIZZLE the chain index is remapped so that each XCD
-// works on one contiguous run of chains (neighbouring chains share node
-// columns of u / x_phys and the partial 128-B lines of y at their ends); a
-// bijection of [0, nwg) for any nwg.  Measured on one MI355X
-// (profiles/r04/xcd/, kernel median ms per action, swizzled / dealt): cfg2
-// 256^2 (2,341 chains) 0.042 / 0.044; the headline 1024^2 (9,472) 0.623 -
-// 0.630 / 0.619 with 0.08 GB less PMC fetch; p = 2 / 4 / 6 / 10 / 16 at 1e7
-// DOF 2-6 % slower.  Off: a run-time choice (a kernel argument) costs the
-// headline kernel, at its register limit, a scratch spill per round.
-#ifndef SEM_XCD_SWIZZLE
-#define SEM_XCD_SWIZZLE 0
-#endif
-__device__ __forceinline__ int64_t xcd_block(int64_t b, int64_t nwg) {
-#if SEM_XCD_SWIZZLE
-  constexpr int64_t NX = 8;
-  const int64_t q = nwg / NX, r = nwg % NX, x = b % NX, k = b / NX;
-  return x * q + (x < r ? x : r) + k;
-#else
-  (void)nwg;
-  return b;
-#endif
+  if (round_sync) __syncthreads();
 }
 
 // ---------------------------------------------------------------------------
@@ -1229,7 +1025,7 @@ __device__ __forceinline__ int64_t xcd_block(int64_t b, int64_t nwg) {
 // profiles/r03/knobs/min_waves_low/); requests at p = 2 / 6 leave their
 // AUTO instantiations' code unchanged, and cfg2 (p = 8 seams) keeps 4.
 // Stored-factor seam kernels at n = 12 / 13 / 15 / 17 (with the transposed
-// D copy, SEM_DEO_TRANSPOSED, the static register tables: n = 12 natural 126
+// D copy, DEOData::TR, the static register tables: n = 12 natural 126
 // VGPRs + 108 SGPRs spilled to lanes, 4-wave request 106 and none; n = 15
 // natural 118 / 4 waves, the old 5-wave request 171 / 2 waves; n = 17
 // natural 161 + 42 spilled, 3-wave request 136 and none).  Measured on one
@@ -1238,51 +1034,22 @@ __device__ __forceinline__ int64_t xcd_block(int64_t b, int64_t nwg) {
 // copy + 3-wave request 0.137 / 0.140, transposed + natural 0.131 / 0.131;
 // p = 14 227^2 0.131 / 0.131 -> 0.129 / 0.129 (natural; the old 5-wave
 // request would now give 2 waves); p = 12 263^2 0.128 / 0.124 -> 0.123 /
-// 0.124; p = 10 316^2 0.121 / 0.120 -> 0.120 / 0.116.  SEM_MW_S<n>
-// overrides the request per order (A/B builds); 0 = the default below.
-#ifndef SEM_MW_S12
-#define SEM_MW_S12 0
-#endif
-#ifndef SEM_MW_S13
-#define SEM_MW_S13 0
-#endif
-#ifndef SEM_MW_S15
-#define SEM_MW_S15 0
-#endif
-#ifndef SEM_MW_S17
-#define SEM_MW_S17 0
-#endif
-constexpr int stored_seam_mw(int n) {
-  return n == 12 ? (SEM_MW_S12 ? SEM_MW_S12 : (SEM_DEO_TRANSPOSED ? 4 : 1))
-       : n == 13 ? (SEM_MW_S13 ? SEM_MW_S13 : 1)
-       : n == 15 ? (SEM_MW_S15 ? SEM_MW_S15 : (SEM_DEO_TRANSPOSED ? 1 : 5))
-       : n == 17 ? (SEM_MW_S17 ? SEM_MW_S17 : 1)
-                 : 1;
-}
+// 0.124; p = 10 316^2 0.121 / 0.120 -> 0.120 / 0.116.
+constexpr int stored_seam_mw(int n) { return n == 12 ? 4 : 1; }
 // the stored seam kernels with D as constants (CD): p = 12 (n = 13) with a
 // 5-wave request (96 VGPRs, 16 B of scratch) measured 0.109-0.110 against
 // 0.123-0.124 ms per action (natural 4 waves; profiles/r04/const_d/l_*);
 // the same request at n = 11 0.117 against 0.108, at n = 15 no change;
 // p = 9 (n = 10) with constants and 5 waves 0.1123-0.1125 against
-// 0.1141 for the argument form (call N).  SEM_MW_CD_N / _W override one
-// order (A/B builds).
-#ifndef SEM_MW_CD_N
-#define SEM_MW_CD_N 0
-#endif
-#ifndef SEM_MW_CD_W
-#define SEM_MW_CD_W 0
-#endif
-constexpr int cd_seam_mw(int n) {
-  return n == SEM_MW_CD_N ? SEM_MW_CD_W : (n == 13 || n == 10) ? 5 : stored_seam_mw(n);
-}
+// 0.1141 for the argument form (call N).
+constexpr int cd_seam_mw(int n) { return (n == 13 || n == 10) ? 5 : stored_seam_mw(n); }
 template <int N, bool NODAL, bool SEAM = false, bool DOT = false, bool CD = false>
 struct PoissonMinWaves {
-  static constexpr int value = SEM_POISSON_MIN_WAVES > 0             ? SEM_POISSON_MIN_WAVES
-                               : (CD && !NODAL && SEAM && !DOT)      ? cd_seam_mw(N)
-                               : (NODAL && N == 9)                   ? 4
-                               : (!NODAL && SEAM && !DOT)            ? stored_seam_mw(N)
-                               : (NODAL && N == 5 && !SEAM && !DOT)  ? 6
-                                                                     : 1;
+  static constexpr int value = (CD && !NODAL && SEAM && !DOT)       ? cd_seam_mw(N)
+                               : (NODAL && N == 9)                  ? 4
+                               : (!NODAL && SEAM && !DOT)           ? stored_seam_mw(N)
+                               : (NODAL && N == 5 && !SEAM && !DOT) ? 6
+                                                                    : 1;
 };
 
 // RawLaunder: which column-kernel instantiations launder their map entries
@@ -1295,12 +1062,9 @@ struct PoissonMinWaves {
 // (7 -> 8 / 6 -> 7 waves); n = 13 / 17 stored seams 106 / 161 -> 102 / 158.
 // Left out: the fused-dot forms (n = 9: 20 -> 36 B of scratch) and n = 11
 // (90 -> 105 VGPRs, 5 -> 4 waves).
-#ifndef SEM_RAW_LAUNDER
-#define SEM_RAW_LAUNDER 1
-#endif
 template <int N, bool DOT>
 struct RawLaunder {
-  static constexpr bool value = SEM_RAW_LAUNDER && !DOT && N != 11;
+  static constexpr bool value = !DOT && N != 11;
 };
 
 struct SeamPlan {
@@ -1309,7 +1073,11 @@ struct SeamPlan {
   int64_t n_node;
   double* dot = nullptr;  // DOT kernels: one partial of u.y per workgroup
   int round_sync = 1;     // a chain writes some node in two rounds: order the rounds
-  const double* w = nullptr;  // device copy of the weights (SEM_W_SCALAR_LOAD)
+  // device copy of the weights.  No kernel reads it; it stays because
+  // k_poisson_mfma17p loads its grid size from the hidden kernel arguments
+  // that follow this struct, so shrinking the struct changes that kernel's
+  // code (the load's offset)
+  const double* w = nullptr;
 };
 
 // sum of one value per thread over the workgroup, in a fixed order (wave
@@ -1335,14 +1103,13 @@ __global__ void __launch_bounds__(ChainWaves<N>::block, (PoissonMinWaves<N, NODA
                     double* __restrict__ y, int64_t c0, int64_t c1, int rounds, int accumulate,
                     const DEO<N> Darg, const WVec<N> w, const SeamPlan sp) {
   const auto D = deo_view<N, CD>(Darg);
-  using T = Tile<N, NODAL ? SEM_TILE_PAD_NODAL : stored_pad(N)>;
+  using T = Tile<N, !NODAL && stored_pad(N)>;
   constexpr int NT = NODAL ? 2 : 1;  // tiles per element slot
   constexpr int CW = ChainWaves<N>::value;
-  constexpr bool WL = NODAL ? NodalTile<N>::wl : StoredTile<N>::wl;
-  constexpr int PLANE = WL ? CW * WLTile<N>::WS : T::TILE_SLOTS * T::ES;  // doubles per tile plane
+  constexpr int PLANE = T::TILE_SLOTS * T::ES;  // doubles per tile plane
   __shared__ __attribute__((aligned(16))) double lds[PLANE * NT];
   __shared__ double carry[CARRY_BUFS][CW][1][N];
-  const int64_t chain = c0 + xcd_block(blockIdx.x, gridDim.x);
+  const int64_t chain = c0 + blockIdx.x;
   if (chain >= c1) {  // uniform over the workgroup
     if constexpr (DOT)
       if (threadIdx.x == 0) sp.dot[blockIdx.x] = 0.0;
@@ -1357,7 +1124,7 @@ __global__ void __launch_bounds__(ChainWaves<N>::block, (PoissonMinWaves<N, NODA
   // tile planes: all of tile A, then all of tile B (interleaving A/B per
   // slot doubles the stride and makes the column accesses 2-way bank
   // conflicts)
-  double* L = lds + (WL ? WLTile<N>::base(wave, k) : T::slot(wave, k, in_wave) * T::ES);
+  double* L = lds + T::slot(wave, k, in_wave) * T::ES;
   double* LB = L + (NT - 1) * PLANE;
   const double wj = pick<N>(w, j);
   double rowc[1] = {0.0};
@@ -1365,17 +1132,13 @@ __global__ void __launch_bounds__(ChainWaves<N>::block, (PoissonMinWaves<N, NODA
     const int64_t g = (chain * rounds + rd) * CW + wave;
     uint32_t raw[N];
     double v[1][N], prev[N];
-    constexpr bool TOUCH = SEM_MAP_TOUCH && M16 && !DOT;
-    MapTouch<N> touch;
-    if constexpr (TOUCH)
-      if (rd + 1 < rounds) touch.issue(mref, g + CW, lane);
     using Pre = typename std::conditional<SEAM, NoPrefetch, NoWait>::type;
     const Pre pre{};
-    constexpr bool PRE = RmwPrefetch<N>::value > 0 && Pre::prefetch;
+    constexpr bool PRE = RmwPrefetch<N>::value && Pre::prefetch;
     constexpr bool LD = RawLaunder<N, DOT>::value;
     if constexpr (NODAL)
       poisson_group_nodal<N, M16, Pre, LD, PAT>(mref, XG, u, g, lane, j, in_wave, L, LB, D, w, wj, raw,
-                                           v[0], y, accumulate, prev, pre, sp.w);
+                                           v[0], y, accumulate, prev, pre);
     else
       poisson_group_stored<N, M16, Pre, LD, PAT>(mref, GP, u, g, lane, j, in_wave, L, D, raw, v[0], y,
                                             accumulate, prev, pre);
@@ -1383,8 +1146,6 @@ __global__ void __launch_bounds__(ChainWaves<N>::block, (PoissonMinWaves<N, NODA
     if constexpr (SEAM) so.base = sp.buf + sp.colour[chain] * sp.n_node;
     chain_emit<N, 1, PRE, CW, SEAM, DOT, LD, CD>(y, raw, v, lane, wave, rd, in_wave, carry, rowc,
                                          accumulate, sp.round_sync, prev, so, u, &dotv);
-    if constexpr (TOUCH)
-      if (rd + 1 < rounds) touch.done();
   }
   if constexpr (DOT) {
     __shared__ double sh[CW];
@@ -1800,9 +1561,6 @@ __device__ __forceinline__ void axisym_group(const uint32_t* __restrict__ mapP,
 #ifndef SEM_AXI_MIN_WAVES
 #define SEM_AXI_MIN_WAVES 1
 #endif
-#ifndef SEM_AXI_EARLY_U
-#define SEM_AXI_EARLY_U 0
-#endif
 template <int N, bool M16, bool PAT = false>
 __device__ __forceinline__ void axisym_group_nodal(const MapRef& mref,
                                                    const double2* __restrict__ XG,
@@ -1817,14 +1575,6 @@ __device__ __forceinline__ void axisym_group_nodal(const MapRef& mref,
   gather_x<N>(XG, raw, j, xc);
   const double2* u2 = reinterpret_cast<const double2*>(u);
   double ps[N], om[N];
-#if SEM_AXI_EARLY_U
-#pragma unroll
-  for (int r = 0; r < N; ++r) {
-    const double2 val = u2[raw[r] & GID_MASK];
-    ps[r] = val.x;
-    om[r] = val.y;
-  }
-#endif
   // Jacobian: jr = d(x, y)/dr along the column, js = d(x, y)/ds along the row
   double jr0[N], jr1[N], js0[N], js1[N], rho[N];
   {
@@ -1866,14 +1616,12 @@ __device__ __forceinline__ void axisym_group_nodal(const MapRef& mref,
     js0[m] = LP[m * RS + j];
     js1[m] = LO[m * RS + j];
   }
-#if !SEM_AXI_EARLY_U
 #pragma unroll
   for (int r = 0; r < N; ++r) {
     const double2 val = u2[raw[r] & GID_MASK];
     ps[r] = val.x;
     om[r] = val.y;
   }
-#endif
   double d0p[N], d0o[N];
   deo_apply<N>(D, ps, d0p);
   deo_apply<N>(D, om, d0o);
@@ -1964,9 +1712,6 @@ __device__ __forceinline__ void axisym_group_nodal(const MapRef& mref,
 // the fields -- the live set drops from 256 VGPRs (one or two waves per SIMD)
 // to the three-wave range.  Same arithmetic, same order per node as
 // axisym_group_nodal.
-#ifndef SEM_AXI_FIELDS_FIRST
-#define SEM_AXI_FIELDS_FIRST 1
-#endif
 template <int N, bool M16, bool PAT = false>
 __device__ __forceinline__ void axisym_group_nodal3(const MapRef& mref,
                                                     const double2* __restrict__ XG,
@@ -1977,7 +1722,6 @@ __device__ __forceinline__ void axisym_group_nodal3(const MapRef& mref,
                                                     uint32_t (&raw)[N], double (&vo)[N],
                                                     double (&vp)[N]) {
   constexpr int RS = Tile<N>::RS;
-  constexpr bool SP = SEM_LDS_SPLIT_AXI;
   load_map<N, M16, false, PAT>(mref, g, lane, in_wave, raw);
   const double2* u2 = reinterpret_cast<const double2*>(u);
   double om[N], d0p[N], d0o[N];
@@ -2018,7 +1762,7 @@ __device__ __forceinline__ void axisym_group_nodal3(const MapRef& mref,
     wave_sync();
     row_pass<N, RS, false, true>(LG, j, D);
 #pragma unroll
-    for (int m = 0; m < N; ++m) js0[m] = lds_ld<SP>(LG + m * RS + j);
+    for (int m = 0; m < N; ++m) js0[m] = LG[m * RS + j];
     wave_sync();
 #pragma unroll
     for (int r = 0; r < N; ++r) LG[r * RS + j] = xc[r].y;
@@ -2026,12 +1770,12 @@ __device__ __forceinline__ void axisym_group_nodal3(const MapRef& mref,
   wave_sync();
   row_pass<N, RS, false, true>(LG, j, D);
 #pragma unroll
-  for (int m = 0; m < N; ++m) js1[m] = lds_ld<SP>(LG + m * RS + j);
+  for (int m = 0; m < N; ++m) js1[m] = LG[m * RS + j];
   // pointwise (squirmer-axisymmetric.py:193-227), as axisym_group_nodal
 #pragma unroll
   for (int m = 0; m < N; ++m) {
-    const double d1p = lds_ld<SP>(LP + m * RS + j);
-    const double d1o = lds_ld<SP>(LO + m * RS + j);
+    const double d1p = LP[m * RS + j];
+    const double d1o = LO[m * RS + j];
     const double det = jr0[m] * js1[m] - js0[m] * jr1[m];
     const double wm = w.v[m];
     const double rs = rho[m] * (wm * (wj * fast_rcp(det)));
@@ -2064,8 +1808,8 @@ __device__ __forceinline__ void axisym_group_nodal3(const MapRef& mref,
   row_pass<N, RS, true, false>(LO, j, D);
 #pragma unroll
   for (int p = 0; p < N; ++p) {
-    vo[p] += lds_ld<SP>(LO + p * RS + j);
-    vp[p] += lds_ld<SP>(LP + p * RS + j);
+    vo[p] += LO[p * RS + j];
+    vp[p] += LP[p * RS + j];
   }
   wave_sync();
 }
@@ -2075,7 +1819,7 @@ __device__ __forceinline__ void axisym_group_nodal3(const MapRef& mref,
 // occupancy than the registers gain
 template <int N>
 struct AxiNodal {
-  static constexpr bool fields_first = SEM_AXI_FIELDS_FIRST && N <= 8;
+  static constexpr bool fields_first = N <= 8;
   static constexpr int planes = fields_first ? 3 : 2;
   static constexpr int waves = fields_first ? (SEM_AXI_MIN_WAVES > 1 ? SEM_AXI_MIN_WAVES : 3)
                                             : SEM_AXI_MIN_WAVES;

@@ -609,7 +609,7 @@ bool build_map16(const Plan& P, int n, std::vector<uint16_t>& m16, std::vector<u
 bool build_map_patterns(std::vector<uint16_t>& m16, std::vector<uint32_t>& mb, int n,
                         int64_t n_slots, int64_t* n_pat) {
   *n_pat = 0;
-  if (!map_pattern_order(n) || SEM_MAP_TOUCH) return false;
+  if (!map_pattern_order(n)) return false;
   const int Q = map_pattern_id_rows(n);  // bases carrying the id
   const int lw = epw_of(n) * n;
   const uint32_t max_pat = 1u << (4 * Q);

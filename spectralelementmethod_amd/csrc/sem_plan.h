@@ -54,11 +54,6 @@ constexpr bool map_pattern_order(int n) {
   return n >= 3 && n <= 31 && ((SEM_MAP_PATTERN_N >> n) & 1u);
 }
 constexpr int map_pattern_id_rows(int n) { return n - 1 < 4 ? n - 1 : 4; }
-// next-round map prefetch (MapTouch, sem_kernels.h): reads the per-group
-// 16-bit entries, so the planner builds no pattern table with it
-#ifndef SEM_MAP_TOUCH
-#define SEM_MAP_TOUCH 0
-#endif
 
 constexpr int MAX_COLOURS = 8;  // + one trailing all-atomic class
 // AUTO choice of the seam plan (Poisson column kernel), from the MI355X A/B

@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """LDS bank model of the column kernel's element tiles (csrc/sem_kernels.h
-Tile / StoredTile): LDS-array cycles per wave-instruction, relative to the
+Tile / stored_pad): LDS-array cycles per wave-instruction, relative to the
 conflict-free count, for the four access shapes of a group -- column reads
 (ds_read_b64, lane (k, j) reads row r of its slot), row reads (lane j reads
 row j: ds_read_b128 pairs when the row stride is even, else ds_read_b64),
