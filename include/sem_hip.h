@@ -763,6 +763,62 @@ int sem_faces_assemble(sem_faces* faces, const double* d_vals, double* d_out, in
  * Writes min(n_info, 7) values. */
 int sem_faces_info(sem_faces* faces, int64_t* info, int n_info);
 
+/* ------------------------------------------------------------------ */
+/* Element matrices: the dense local systems of the assembled path      */
+/* ------------------------------------------------------------------ */
+/* The dense element operators the reference builds per element in Python --
+ * Lse (examples/poisson.py:166-193) and the Newton system jac_l / -res_l of
+ * compute_local_system (examples/squirmer-axisymmetric.py:259-297) -- for the
+ * elements [elem_begin, elem_begin + elem_count) in one launch.  Quadrilaterals
+ * (ndim = 2), 1 <= p <= 16.  op_kind: SEM_OP_POISSON (dpn = 1),
+ * SEM_OP_AXISYM_STOKES (dpn = 2), SEM_OP_AXISYM_NS (dpn = 2; `re` and d_state
+ * required).  nl = dpn * n * n; local DOF dpn * (i * n + j) + comp, as
+ * FiniteElement.loc_dof_ind_hier assumes (sem/discrete.py:562-571).
+ *
+ * d_mat: float64 [elem_count][nl][nl].  Column k of an element's matrix is
+ * what the action of the kind (sem_apply) gives for that element alone on the
+ * k-th local unit vector:
+ *   Poisson  A[(p,q),(r,s)] = d_qs sum_m G00[m,q] D[m,p] D[m,r]
+ *                           + G01[r,q] D[r,p] D[q,s] + G01[p,s] D[s,q] D[p,r]
+ *                           + d_pr sum_n G11[p,n] D[n,q] D[n,s];
+ *   Stokes   jac_l at Re = 0 (squirmer :276-291): rows 0::2 (the omega
+ *            equation) hold Lve in the columns 1::2, rows 1::2 (the psi
+ *            equation) E2e in the columns 0::2 and -Me in the columns 1::2;
+ *   Navier-Stokes  the same plus d(Ae omega psi)/d psi in [0::2, 0::2] and
+ *            d/d omega in [0::2, 1::2] at d_state, the global vector
+ *            interleaved (psi, omega) gathered through d_e2n (the five
+ *            coefficients per node of SEM_OP_AXISYM_NS_JVP).
+ * d_rhs: float64 [elem_count][nl] or NULL; needs d_state: minus the
+ * element-local residual of the kind at the state, the reference's -res_l
+ * (-A_e u_e for the two linear kinds, which read d_state for nothing else).
+ *
+ * h_local_order: nl entries or NULL (lexicographic): row and column a of the
+ * output are local DOF h_local_order[a], so the hierarchical order of
+ * reorder_local_system_hier (sem/discrete.py:428-436) is written directly.
+ * d_x_phys: float64 [n_elem][2][n][n] exactly as sem_geom_fields writes it;
+ * d_e2n: uint32 [n_elem][n][n]; h_D [n][n], h_w [n] as in sem_faces_create
+ * (read before the call returns).  The per-node factors are derived from
+ * x_phys as the stored ones are (sem_geom_from_nodes); the context's packed
+ * geometry is not read.  Non-finite values on the axis: W / rho at rho = 0 is
+ * formed exactly as the stored factors form it and propagates as there
+ * (squirmer :217-221, the reference divides by rho as well); there is no
+ * special case.  The state's size (2 * (max(d_e2n) + 1) entries, one per node
+ * for Poisson) is the caller's obligation, as in sem_points_eval;
+ * SEMOperator.element_matrices refuses a state of any other size.
+ *
+ * Checked before any device call: SEM_E_INVALID for NULL arrays, p < 1, a
+ * range outside [0, n_elem], an order that is not a permutation of 0..nl-1,
+ * d_rhs without d_state, SEM_OP_AXISYM_NS without d_state, an unknown kind;
+ * SEM_E_NOTIMPL for p > 16, ndim != 2, SEM_OP_AXISYM_NS_JVP as a kind.  All
+ * indexing is int64: the batch is [elem_count] x 52 KB at p = 8 scalar, 2.7 MB
+ * at p = 16 with two DOFs per node, hence the range.  One launch on the
+ * current device; allocates nothing and does not synchronise
+ * (graph-capturable, like sem_apply). */
+int sem_elem_matrices(int op_kind, int ndim, int p, int64_t n_elem, const double* d_x_phys,
+                      const double* h_D, const double* h_w, double re, const uint32_t* d_e2n,
+                      const double* d_state, const int32_t* h_local_order, int64_t elem_begin,
+                      int64_t elem_count, double* d_mat, double* d_rhs, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

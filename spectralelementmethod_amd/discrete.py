@@ -788,12 +788,41 @@ class DOFManagerSC(DOFManager):
         S, s, _ = _schur_batched([local_system], fe.ndof_exterior)
         return S[0].cpu().numpy(), s[0].cpu().numpy()
 
+    def local_systems(self, kind, state=None):
+        """The local systems of every element for ``kind`` on the device, in
+        hierarchical order (reorder_local_system_hier of compute_local_system,
+        examples/squirmer-axisymmetric.py:259-297, for all elements in one
+        launch): kind "poisson" (rhs = -Lse u, or zero without a state),
+        "axisym_stokes", "axisym_ns" (the Newton system at ``state``: jac_l,
+        -res_l; the Reynolds number is the operator's, set_reynolds)."""
+        import torch
+        from .operators import AXISYM_NS, op_kind
+        op = self.operator()
+        kind = op_kind(kind)
+        if state is None and kind != AXISYM_NS:
+            mats = op.element_matrices(kind, order="hier")
+            rhs = torch.zeros(mats.shape[:2], dtype=torch.float64, device=mats.device)
+        else:
+            mats, rhs = op.element_matrices(kind, state=state, order="hier", rhs=True)
+        return LocalSystems(mats, rhs)
+
     def assemble_global_sc_system(self, global_sc_system, local_systems):
         """Element Schur complements of all local systems (one batched
         device launch) assembled into the COO system from
         init_global_linear_system (sem/discrete.py:474-500)."""
         gmat, grhs = global_sc_system
         dofs, ne = self._cell_dofs_hier()
+        if isinstance(local_systems, LocalSystems):
+            # device tensors: no stack, no upload
+            S, s, work = _schur_device(local_systems.mats, local_systems.rhs, ne)
+            ext = dofs[:, :ne]
+            gmat.row[:] = np.repeat(ext, ne, axis=1).ravel()
+            gmat.col[:] = np.tile(ext, (1, ne)).ravel()
+            gmat.data[:] = S.reshape(ext.shape[0], -1).cpu().numpy().ravel()
+            grhs += np.bincount(ext.ravel(), weights=s.cpu().numpy().ravel(),
+                                minlength=grhs.size)
+            self._sc_state = (local_systems, (local_systems.mats, local_systems.rhs), work, ne)
+            return
         local_systems = list(local_systems) if not isinstance(local_systems, list) \
             else local_systems
         S, s, work = _schur_batched(local_systems, ne, self._device)
@@ -852,7 +881,13 @@ class DOFManagerSC(DOFManager):
         from . import _lib
         dofs, ne = self._cell_dofs_hier()
         st = getattr(self, "_sc_state", None)
-        if st is None or st[0] is not local_systems or \
+        if isinstance(local_systems, LocalSystems):
+            if st is not None and st[0] is local_systems and \
+                    st[1][0] is local_systems.mats and st[1][1] is local_systems.rhs:
+                work = st[2]
+            else:
+                _, _, work = _schur_device(local_systems.mats, local_systems.rhs, ne)
+        elif st is None or st[0] is not local_systems or \
                 (local_systems and st[1] is not local_systems[0]):
             _, _, work = _schur_batched(list(local_systems), ne, self._device)
         else:
@@ -895,19 +930,61 @@ class DOFManagerSC(DOFManager):
         return dof_vec, its, rel
 
 
+class LocalSystems(object):
+    """The hierarchical-order local systems of every element as device
+    tensors (DOFManagerSC.local_systems): ``mats`` [E, nl, nl], ``rhs``
+    [E, nl].  len() and [i] give the reference-style (lmat, lrhs) NumPy pair
+    of one element (sem/discrete.py:428-436); ``rhs`` may be replaced by the
+    caller's own tensor or array (Poisson: detJxW for f = 1)."""
+
+    def __init__(self, mats, rhs):
+        self.mats = mats
+        self._rhs = None
+        self.rhs = rhs
+
+    @property
+    def rhs(self):
+        return self._rhs
+
+    @rhs.setter
+    def rhs(self, value):
+        import torch
+        E, nl = self.mats.shape[0], self.mats.shape[1]
+        if not isinstance(value, torch.Tensor):
+            value = torch.from_numpy(np.ascontiguousarray(value, dtype=np.float64))
+        if value.dtype != torch.float64 or value.numel() != E * nl:
+            raise ValueError("rhs must hold float64 [%d, %d]" % (E, nl))
+        self._rhs = value.to(self.mats.device).reshape(E, nl).contiguous()
+
+    def __len__(self):
+        return int(self.mats.shape[0])
+
+    def __getitem__(self, i):
+        if not -len(self) <= i < len(self):
+            raise IndexError(i)
+        return self.mats[i].cpu().numpy(), self._rhs[i].cpu().numpy()
+
+
 def _schur_batched(local_systems, ne, device=None):
     """Device Schur complements of hierarchical local systems (list of
     (lmat [nl, nl], lrhs [nl])): returns S [E, ne, ne], s [E, ne] and the
     elimination workspace (A_ii^-1 [A_ie | b_i]) as device tensors."""
-    import ctypes as C
     import torch
-    from . import _lib
     from .operators import _device_index
     dev = torch.device("cuda", _device_index(device))
     mats = torch.from_numpy(np.ascontiguousarray(
         np.stack([np.asarray(m, dtype=np.float64) for m, _ in local_systems]))).to(dev)
     rhs = torch.from_numpy(np.ascontiguousarray(
         np.stack([np.asarray(r, dtype=np.float64) for _, r in local_systems]))).to(dev)
+    return _schur_device(mats, rhs, ne)
+
+
+def _schur_device(mats, rhs, ne):
+    """_schur_batched on device tensors mats [E, nl, nl], rhs [E, nl]."""
+    import ctypes as C
+    import torch
+    from . import _lib
+    dev = mats.device
     E, nl = rhs.shape
     if mats.shape != (E, nl, nl) or not (0 <= ne <= nl):
         raise ValueError("local systems must be [nl, nl] matrices and [nl] vectors")

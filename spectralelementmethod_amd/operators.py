@@ -381,7 +381,94 @@ class SEMOperator(object):
     def set_reynolds(self, re):
         """Reynolds number of the Navier-Stokes kinds (squirmer n_rey)."""
         _lib.check(self._lib.sem_set_reynolds(self._ctx, float(re)))
+        self._re = float(re)
         return self
+
+    def local_order(self, order, kind=POISSON):
+        """Local DOF order of the element matrices as int32 [nl]: "lex", "hier"
+        (FiniteElement.loc_dof_ind_hier: element-exterior nodes first,
+        sem/discrete.py:562-571) or an explicit permutation."""
+        dpn = 1 if op_kind(kind) == POISSON else 2
+        nl = dpn * self.n ** 2
+        if isinstance(order, str):
+            if order == "lex":
+                return np.arange(nl, dtype=np.int32)
+            if order != "hier":
+                raise ValueError("order must be 'lex', 'hier' or a permutation of %d DOFs" % nl)
+            from .geometry import Quadrilateral
+            h = Quadrilateral(self.n, self.n).hierarchical_node_order.astype(np.int64)
+            return (dpn * h[:, None] + np.arange(dpn)[None, :]).ravel().astype(np.int32)
+        o = np.ascontiguousarray(order).astype(np.int32).ravel()
+        if o.size != nl:
+            raise ValueError("order has %d entries, the local systems %d DOFs" % (o.size, nl))
+        return o
+
+    def element_matrices(self, kind=POISSON, state=None, order="lex", elems=None, rhs=False,
+                         out=None, stream=None):
+        """Dense element matrices [count, nl, nl] of ``kind`` as a device
+        tensor (sem_elem_matrices): Lse of examples/poisson.py:166-193, jac_l
+        of examples/squirmer-axisymmetric.py:259-297 (kind "axisym_ns": at
+        ``state``, with the Reynolds number of set_reynolds).  nl = dpn n^2
+        with dpn = 1 (Poisson) or 2; ``order``: see local_order; ``elems`` =
+        (begin, count) selects a range of elements (default: all).  With
+        rhs=True returns (matrices, -residual at ``state`` [count, nl]).
+        ``out``: the matrices' tensor, or the pair with rhs=True.  ``state``
+        is the global vector of the kind (n_node entries for Poisson,
+        interleaved 2 n_node otherwise); any other size raises ValueError,
+        since the kernel indexes it with the mesh's map."""
+        kind = op_kind(kind)
+        if kind == AXISYM_NS_JVP:
+            raise NotImplementedError("element_matrices: the Jacobian is the matrix of 'axisym_ns'")
+        if self.ndim != 2:
+            raise NotImplementedError("element_matrices: quadrilaterals")
+        dpn = 1 if kind == POISSON else 2
+        nl = dpn * self.n ** 2
+        begin, count = (0, self.n_elem) if elems is None else (int(elems[0]), int(elems[1]))
+        if begin < 0 or count < 0 or begin + count > self.n_elem:
+            raise ValueError("elems = (begin, count) must lie in [0, %d]" % self.n_elem)
+        if (rhs or kind == AXISYM_NS) and state is None:
+            raise ValueError("element_matrices: kind 'axisym_ns' and rhs=True need a state")
+        if state is not None:
+            if not isinstance(state, torch.Tensor):
+                state = torch.as_tensor(np.ascontiguousarray(state, dtype=np.float64))
+            if state.dtype != torch.float64:
+                raise TypeError("state must be float64")
+            state = state.to(self.device).contiguous()
+            if state.dim() != 1 or state.numel() != dpn * self.n_node:
+                raise ValueError("state must be 1-D with %d * n_node = %d entries, got shape %s"
+                                 % (dpn, dpn * self.n_node, list(state.shape)))
+        order = self.local_order(order, kind)
+        kw = dict(dtype=torch.float64, device=self.device)
+        mats, vec = (out if rhs else (out, None)) if out is not None else (None, None)
+
+        def _out(t, shape, name):
+            if t is None:
+                return torch.empty(shape, **kw)
+            if not (isinstance(t, torch.Tensor) and t.dtype == torch.float64
+                    and t.device == self.device and t.is_contiguous()
+                    and tuple(t.shape) == shape):
+                raise TypeError("%s must be a contiguous float64 tensor of shape %s on %s"
+                                % (name, list(shape), self.device))
+            return t
+        mats = _out(mats, (count, nl, nl), "out")
+        vec = _out(vec, (count, nl), "out[1]") if rhs else None
+        if count == 0:
+            return (mats, vec) if rhs else mats
+        if getattr(self, "_elmat_x", None) is None:
+            if self.geometry == "reference":
+                x = torch.from_numpy(reference_x_phys(self.nodes.cpu().numpy(),
+                                                      self.e2n.cpu().numpy().view(np.uint32),
+                                                      self.basis)).to(self.device)
+            else:
+                x = self.geometry_fields(stream=stream)["x_phys"]
+            self._elmat_x = x.contiguous()
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.sem_elem_matrices(
+                kind, self.ndim, self.p, self.n_elem, _lib.tptr(self._elmat_x), _lib.dptr(self.D),
+                _lib.dptr(self.w), float(getattr(self, "_re", 0.0)), _lib.tptr(self.e2n),
+                _lib.tptr(state), order.ctypes.data_as(C.POINTER(C.c_int32)), begin, count,
+                _lib.tptr(mats), _lib.tptr(vec), self._stream(stream)))
+        return (mats, vec) if rhs else mats
 
     def apply(self, u, out=None, kind=POISSON, accumulate=False, stream=None, linearize=False,
               renumber=False):
