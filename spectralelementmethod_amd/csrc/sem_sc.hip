@@ -62,6 +62,7 @@ __global__ void __launch_bounds__(SCB)
       X[t] = j < ni ? A[(int64_t)row * nl + ne + j]
                     : (j < ni + ne ? A[(int64_t)row * nl + (j - ni)] : b[row]);
     }
+    __syncthreads();  // the scan below reads entries other threads filled
     // The reference (scipy linalg.solve, check_finite=False) raises when the
     // interior block holds a NaN or an off-diagonal inf (LAPACK reports the
     // block singular or an illegal value) but lets an infinite diagonal entry
