@@ -36,16 +36,9 @@
 
 #include <cstdint>
 
+#include "sem_hex_plan.h"
+
 namespace semh {
-
-constexpr int HEX_MIN_N = 2;
-constexpr int HEX_MAX_N = 17;  // p <= 16
-
-// element slots per workgroup: as many n x n thread tiles as fit in 256 threads
-constexpr int hex_slots(int n) { return 256 / (n * n) > 0 ? 256 / (n * n) : 1; }
-constexpr int hex_threads(int n) { return (hex_slots(n) * n * n + 63) / 64 * 64; }
-// boundary columns of an element: b or c on the element boundary
-constexpr int hex_nbc(int n) { return 4 * (n - 1); }
 
 // launch tables of the hex plan (device pointers; sem_hex.hip builds them)
 struct HexLaunch {
@@ -53,10 +46,9 @@ struct HexLaunch {
   const int* wg_len;                // [n_wg] chain length of workgroup w
   const int* elist;                 // [pos] element at position wg_off + k*S + s, -1 = empty slot
   const unsigned long long* cmask;  // [pos] boundary columns written into slots
-  const uint8_t* cflag;             // [n_wg*S] bit 0: chain head face slotted, bit 1: tail face,
-                                    // bit 2: the sub-chain's xi2 = 0 face is the xi2 = n-1
-                                    // face of slot s-1's (z-merge: summed in LDS)
+  const uint8_t* cflag;             // [n_wg*S] HEX_CF_* of the sub-chain in slot s
   double* slot;                     // column slots [pos][n][NBC], then face slots [n_wg*S][2][n^2]
+                                    // (hex_col_slot / hex_face_slot)
   int64_t face_base;
   // template map (the TM kernels): every element's node ids are its first
   // node's id + one shared offset block -- a structured numbering -- so a
@@ -71,28 +63,8 @@ enum { HEX_SET = 0, HEX_ACC = 1, HEX_DIAG = 2 };
 // z-merge (xi2 faces between the slots of a workgroup summed in LDS, one
 // writer fewer per merged node) in the three-block kernel: the exchange
 // goes through its w1 block (no LDS of its own); the plan decides at run
-// time (SEM_HEX_ZMERGE=0 in the environment turns it off); building with
-// -DSEM_HEX_ZMERGE=0 removes the code
-#ifndef SEM_HEX_ZMERGE
-#define SEM_HEX_ZMERGE 1
-#endif
-constexpr bool HEX_ZMERGE = SEM_HEX_ZMERGE != 0;
-
-// y-merge (three-block kernel, with the z-merge): the S slots of a
-// workgroup form a Y x Z grid (Z = hex_grid_z(n) slots along xi2 per row, Y
-// rows along xi1; Y = 1 when S is prime), and slot s hands its xi1 = 0 face
-// to slot s - Z when that face IS slot s - Z's xi1 = n-1 face at every chain
-// step (cflag bit 3, checked by the planner), through the w2 block.  Columns
-// a slot already handed over in the z-merge (c = 0) stay out of the y-merge
-// on both sides.  p = 1 / 2 / 3 / 4 / 7: 8 x 8, 4 x 7, 4 x 4, 2 x 5, 2 x 2
-// slots; on by default at p <= 3 (sem_hex.hip ctx_init), SEM_HEX_YMERGE=1 / 0
-// in the environment forces it.
-constexpr int hex_grid_z(int n) {
-  int z = hex_slots(n);
-  for (int y = 2; y * y <= hex_slots(n); ++y)
-    if (hex_slots(n) % y == 0) z = hex_slots(n) / y;
-  return z;
-}
+// time (SEM_HEX_ZMERGE=0 in the environment turns it off).  y-merge:
+// hex_grid_z, sem_hex_plan.h.
 
 // D as a kernel argument: the wave-uniform coefficients of the
 // register-direction contractions (row a of D, for d0 = D u and y += D^T w0
@@ -104,54 +76,55 @@ struct HexD {
 };
 
 // Layout of the stored factors (G00, G01, G02, G11, G12, G22 per element
-// node) as three double2 pairs (00, 01), (02, 11), (12, 22).  SoA
-// (HEX_GSOA, default): per element and node row a, three planes of n^2
-// pairs, so one wave-instruction reads 64 lanes' pair j as one contiguous
-// 1 KiB run; AoS (SEM_HEX_GSOA=0): the node's three pairs side by side
-// (48 B per lane, each wave-instruction spread over 3 KiB).  Measured equal
-// at p = 4..10 and 1.5 % faster at p = 2.  Either way a
-// node row is 3 n^2 pairs.
-#ifndef SEM_HEX_GSOA
-#define SEM_HEX_GSOA 1
-#endif
-constexpr bool HEX_GSOA = SEM_HEX_GSOA != 0;
+// node) as three double2 pairs (00, 01), (02, 11), (12, 22), SoA: per element
+// and node row a, three planes of n^2 pairs (a node row is 3 n^2 pairs), so
+// one wave-instruction reads 64 lanes' pair j as one contiguous 1 KiB run.
+// (The node's three pairs side by side, 48 B per lane, measured equal at
+// p = 4..10 and 1.5 % slower at p = 2)
 template <int N>
 __host__ __device__ constexpr int64_t hex_g_off(int64_t e, int bc) {
-  return e * (int64_t)N * N * N * 3 + (HEX_GSOA ? bc : 3 * bc);
+  return e * (int64_t)N * N * N * 3 + bc;
 }
 template <int N>
 __device__ __forceinline__ const double2* hex_g(const double* G, int64_t e, int bc) {
   return reinterpret_cast<const double2*>(G) + hex_g_off<N>(e, bc);
 }
 
-// boundary-column index of (b, c) in [0, 4(n-1)), -1 for an interior column
+// hex_bcol (sem_hex_plan.h) with n a template argument, the kernels' copy:
+// calling the shared function with n = N changes the instructions the
+// compiler emits for every element kernel (same values, another block
+// order), so the kernels keep this one and the static_assert ties the two
 template <int N>
-__device__ __forceinline__ int hex_bcol(int b, int c) {
+__device__ __forceinline__ constexpr int hex_bcol_n(int b, int c) {
   if (b == 0) return c;
   if (b == N - 1) return 3 * N - 4 + c;
   if (c == 0) return N + 2 * (b - 1);
   if (c == N - 1) return N + 2 * (b - 1) + 1;
   return -1;
 }
+template <int N>
+constexpr bool hex_bcol_agrees() {
+  for (int b = 0; b < N; ++b)
+    for (int c = 0; c < N; ++c)
+      if (hex_bcol_n<N>(b, c) != hex_bcol(N, b, c)) return false;
+  return true;
+}
 
 // Poisson stiffness action on hexahedra (MODE HEX_SET / HEX_ACC), or the
 // diagonal of the assembled operator (HEX_DIAG; u unused).  G: stored factors
 // in the pair layout of hex_g (components 00, 01, 02, 11, 12, 22): a thread
 // reads its node's six as three 16-byte loads.
-#ifndef SEM_HEX_MIN_WAVES
-#define SEM_HEX_MIN_WAVES 4
-#endif
 // occupancy request: above p = 10 the register arrays (column of u, y, the
 // maps) exceed what four waves per SIMD allow, and one element slot per
 // workgroup leaves LDS the limit anyway
-constexpr int hex_min_waves(int n) { return n <= 11 ? SEM_HEX_MIN_WAVES : n <= 13 ? 2 : 1; }
+constexpr int hex_min_waves(int n) { return n <= 11 ? 4 : n <= 13 ? 2 : 1; }
 template <int N, int MODE, bool TM = false>
 __global__ void __launch_bounds__(hex_threads(N), hex_min_waves(N))
     k_hex_poisson(const double* __restrict__ u, double* __restrict__ y,
                   const uint32_t* __restrict__ map, const double* __restrict__ G,
                   const double* __restrict__ gD, HexLaunch P, const HexD<N> Dk) {
   constexpr int N2 = N * N, N3 = N2 * N, S = hex_slots(N), T = hex_threads(N), NBC = hex_nbc(N);
-  constexpr int GROW = 3 * N2, GPAIR = HEX_GSOA ? N2 : 1;  // factor layout (hex_g)
+  constexpr int GROW = 3 * N2, GPAIR = N2;  // factor layout (hex_g)
   __shared__ double sD[N2];
   __shared__ double sU[S * N3];
   __shared__ double sA[S * N3];
@@ -160,7 +133,6 @@ __global__ void __launch_bounds__(hex_threads(N), hex_min_waves(N))
   // the w1 block, free once every thread has finished the transposed pass
   // (a buffer of its own, 1.3 KB at n = 9, took the workgroup one 512-byte
   // granule past three per CU: element kernel 225 -> 241 us)
-  constexpr bool ZM = HEX_ZMERGE;
   const int tid = threadIdx.x;
   for (int i = tid; i < N2; i += T) sD[i] = gD[i];
   const int w = blockIdx.x;
@@ -174,37 +146,40 @@ __global__ void __launch_bounds__(hex_threads(N), hex_min_waves(N))
   double* const su = sU + sl * N3;
   double* const sa = sA + sl * N3;
   double* const sb = sB + sl * N3;
-  const int bcol = hex_bcol<N>(b, c);
+  static_assert(hex_bcol_agrees<N>(), "hex_bcol_n differs from hex_bcol");
+  const int bcol = hex_bcol_n<N>(b, c);
   const uint8_t cf = active ? P.cflag[w * S + s] : 0;
   // z-merge: slot s hands its xi2 = 0 face to slot s-1, whose xi2 = n-1 face
   // holds the same nodes in the same (a, b) order (the planner checked every
   // chain step); the merged node then has one writer fewer
-  const bool give = (cf & 4) && c == 0;
-  [[maybe_unused]] const bool take = active && c == N - 1 && s + 1 < S && (P.cflag[w * S + s + 1] & 4);
+  const bool give = (cf & HEX_CF_ZGIVE) && c == 0;
+  const bool take =
+      active && c == N - 1 && s + 1 < S && (P.cflag[w * S + s + 1] & HEX_CF_ZGIVE);
   // y-merge: slot s hands its xi1 = 0 face (b = 0) to slot s - GZ, except
   // the column it already handed over in the z-merge (or whose receiver did)
   constexpr int GZ = hex_grid_z(N);
-  constexpr bool YM = ZM && GZ < S;
+  constexpr bool YM = GZ < S;
   [[maybe_unused]] bool ygive = false, ytake = false;
   if constexpr (YM) {
-    ygive = (cf & 8) && b == 0 && s >= GZ &&
-            !(c == 0 && ((cf & 4) || (P.cflag[w * S + s - GZ] & 4)));
+    ygive = (cf & HEX_CF_YGIVE) && b == 0 && s >= GZ &&
+            !(c == 0 && ((cf & HEX_CF_ZGIVE) || (P.cflag[w * S + s - GZ] & HEX_CF_ZGIVE)));
     if (active && b == N - 1 && s + GZ < S) {
       const uint8_t cg = P.cflag[w * S + s + GZ];
-      ytake = (cg & 8) && !(c == 0 && ((cg & 4) || (cf & 4)));
+      ytake = (cg & HEX_CF_YGIVE) && !(c == 0 && ((cg & HEX_CF_ZGIVE) || (cf & HEX_CF_ZGIVE)));
     }
   }
-  [[maybe_unused]] bool wg_merge = false;
-  if constexpr (ZM)
+  bool wg_merge = false;
 #pragma unroll
-    for (int t = 1; t < S; ++t) wg_merge |= (P.cflag[w * S + t] & 12) != 0;
+  for (int t = 1; t < S; ++t)
+    wg_merge |= (P.cflag[w * S + t] & (HEX_CF_ZGIVE | HEX_CF_YGIVE)) != 0;
+  // hex_face_slot(N, P.face_base, w, sl, 0, bc); the tail face N2 further
   double* const face = P.slot + P.face_base + (int64_t)(w * S + sl) * 2 * N2 + bc;
   __syncthreads();  // sD
   double carry = 0.0;
   // the element map of the next chain step is loaded one step ahead
   uint32_t mn[N];
   int en = active ? P.elist[base + s] : 0;
-  [[maybe_unused]] int toff[TM ? N : 1];
+  [[maybe_unused]] int toff[TM ? N : 1];  // template map (HexLaunch::tmpl)
   if constexpr (TM)
 #pragma unroll
     for (int a = 0; a < N; ++a) toff[a] = P.tmpl[a * N2 + bc];
@@ -230,13 +205,7 @@ __global__ void __launch_bounds__(hex_threads(N), hex_min_waves(N))
     if (active) {
       if constexpr (MODE != HEX_DIAG) {
 #pragma unroll
-        for (int a = 0; a < N; ++a) {
-#ifdef SEM_HEX_DIAG_NOGATHER  // diagnostic builds only: no u gather
-          uc[a] = (double)m[a];
-#else
-          uc[a] = u[m[a]];
-#endif
-        }
+        for (int a = 0; a < N; ++a) uc[a] = u[m[a]];
 #pragma unroll
         for (int a = 0; a < N; ++a) su[a * N2 + bc] = uc[a];
       } else {
@@ -337,7 +306,7 @@ __global__ void __launch_bounds__(hex_threads(N), hex_min_waves(N))
       }
       __syncthreads();  // su / sa / sb are rewritten by the next element
     }
-    if (ZM && wg_merge) {  // workgroup-uniform
+    if (wg_merge) {  // workgroup-uniform
       // the diagonal branch ends on a barrier already
       if constexpr (MODE != HEX_DIAG) __syncthreads();  // sA / sB reads done
       if (give)
@@ -364,6 +333,8 @@ __global__ void __launch_bounds__(hex_threads(N), hex_min_waves(N))
       if constexpr (MODE == HEX_DIAG) __syncthreads();
     }
     if (active && !give && !ygive) {
+      // the write rule (the planner applies the same: sem_hex_plan.cpp
+      // thread_rows; slots: hex_face_slot / hex_col_slot)
       if (k > 0) yv[0] += carry;
       const bool last = k == L - 1;
       if (!last) carry = yv[N - 1];
@@ -373,12 +344,9 @@ __global__ void __launch_bounds__(hex_threads(N), hex_min_waves(N))
       for (int a = 0; a < N; ++a) {
         if (a == N - 1 && !last) continue;  // carried into the next element's row 0
         const double v = yv[a];
-#ifdef SEM_HEX_DIAG_NOSTORE  // diagnostic builds only: no stores
-        if (!(v != v)) continue;
-#endif
-        if (a == 0 && k == 0 && (cf & 1)) {
+        if (a == 0 && k == 0 && (cf & HEX_CF_HEAD)) {
           face[0] = v;
-        } else if (a == N - 1 && last && (cf & 2)) {
+        } else if (a == N - 1 && last && (cf & HEX_CF_TAIL)) {
           face[N2] = v;
         } else if (colslot) {
           cs[a * NBC] = v;
@@ -416,7 +384,7 @@ __global__ void __launch_bounds__(hex_threads(N), hex_rows_min_waves(N))
   static_assert(MODE == HEX_SET || MODE == HEX_ACC, "row form: the action only");
   constexpr int N2 = N * N, N3 = N2 * N, S = hex_slots(N), T = hex_threads(N), NBC = hex_nbc(N);
   constexpr int SW = S * N2;  // one plane of the ring: [slot][b*n + c]
-  constexpr int GROW = 3 * N2, GPAIR = HEX_GSOA ? N2 : 1;  // factor layout (hex_g)
+  constexpr int GROW = 3 * N2, GPAIR = N2;  // factor layout (hex_g)
   __shared__ double sD[N2];
   __shared__ double sU[S * N3];
   __shared__ double sW[4 * SW];  // [row parity][w1, w2][slot][b*n + c]
@@ -433,15 +401,18 @@ __global__ void __launch_bounds__(hex_threads(N), hex_rows_min_waves(N))
   const bool active = s < S && P.elist[base + s] >= 0;
   const int sl = active ? s : 0;
   double* const su = sU + sl * N3;
-  const int bcol = hex_bcol<N>(b, c);
+  static_assert(hex_bcol_agrees<N>(), "hex_bcol_n differs from hex_bcol");
+  const int bcol = hex_bcol_n<N>(b, c);
   const uint8_t cf = active ? P.cflag[w * S + s] : 0;
-  // z-merge (planner, cflag bit 2): this slot's xi2 = 0 face is slot s-1's
+  // z-merge (planner, HEX_CF_ZGIVE): this slot's xi2 = 0 face is slot s-1's
   // xi2 = n-1 face at every chain step, node for node
-  const bool give = (cf & 4) && c == 0;
-  const bool take = active && c == N - 1 && s + 1 < S && (P.cflag[w * S + s + 1] & 4);
+  const bool give = (cf & HEX_CF_ZGIVE) && c == 0;
+  const bool take =
+      active && c == N - 1 && s + 1 < S && (P.cflag[w * S + s + 1] & HEX_CF_ZGIVE);
   bool wg_merge = false;
 #pragma unroll
-  for (int t = 1; t < S; ++t) wg_merge |= (P.cflag[w * S + t] & 4) != 0;
+  for (int t = 1; t < S; ++t) wg_merge |= (P.cflag[w * S + t] & HEX_CF_ZGIVE) != 0;
+  // hex_face_slot(N, P.face_base, w, sl, 0, bc); the tail face N2 further
   double* const face = P.slot + P.face_base + (int64_t)(w * S + sl) * 2 * N2 + bc;
   __syncthreads();  // sD
   double carry = 0.0;
@@ -537,6 +508,8 @@ __global__ void __launch_bounds__(hex_threads(N), hex_rows_min_waves(N))
         for (int a = 0; a < N; ++a) yv[a] += sX[sl * N2 + a * N + b];
     }
     if (active && !give) {
+      // the write rule (the planner applies the same: sem_hex_plan.cpp
+      // thread_rows; slots: hex_face_slot / hex_col_slot)
       if (k > 0) yv[0] += carry;
       const bool last = k == L - 1;
       if (!last) carry = yv[N - 1];
@@ -546,9 +519,9 @@ __global__ void __launch_bounds__(hex_threads(N), hex_rows_min_waves(N))
       for (int a = 0; a < N; ++a) {
         if (a == N - 1 && !last) continue;  // carried into the next element's row 0
         const double v = yv[a];
-        if (a == 0 && k == 0 && (cf & 1)) {
+        if (a == 0 && k == 0 && (cf & HEX_CF_HEAD)) {
           face[0] = v;
-        } else if (a == N - 1 && last && (cf & 2)) {
+        } else if (a == N - 1 && last && (cf & HEX_CF_TAIL)) {
           face[N2] = v;
         } else if (colslot) {
           cs[a * NBC] = v;
@@ -736,10 +709,10 @@ __global__ void __launch_bounds__(hex_threads(N))
           gp[0] = make_double2(
               W * (iJ[0][0] * iJ[0][0] + iJ[0][1] * iJ[0][1] + iJ[0][2] * iJ[0][2]),
               W * (iJ[0][0] * iJ[1][0] + iJ[0][1] * iJ[1][1] + iJ[0][2] * iJ[1][2]));
-          gp[HEX_GSOA ? N2 : 1] = make_double2(
+          gp[N2] = make_double2(
               W * (iJ[0][0] * iJ[2][0] + iJ[0][1] * iJ[2][1] + iJ[0][2] * iJ[2][2]),
               W * (iJ[1][0] * iJ[1][0] + iJ[1][1] * iJ[1][1] + iJ[1][2] * iJ[1][2]));
-          gp[HEX_GSOA ? 2 * N2 : 2] = make_double2(
+          gp[2 * N2] = make_double2(
               W * (iJ[1][0] * iJ[2][0] + iJ[1][1] * iJ[2][1] + iJ[1][2] * iJ[2][2]),
               W * (iJ[2][0] * iJ[2][0] + iJ[2][1] * iJ[2][1] + iJ[2][2] * iJ[2][2]));
         }
@@ -863,12 +836,8 @@ __global__ void k_hex_pack_geom(const double* __restrict__ G, int64_t n_elem, in
     const int64_t rem = t - e * 6 * n3;
     const int comp = (int)(rem / n3);
     const int64_t node = rem - comp * n3;
-    if (HEX_GSOA) {  // [e][a][pair][bc][2]
-      const int64_t a = node / n2, bc = node - a * n2;
-      GP[(((e * n + a) * 3 + comp / 2) * n2 + bc) * 2 + (comp & 1)] = G[t];
-    } else {
-      GP[(e * n3 + node) * 6 + comp] = G[t];
-    }
+    const int64_t a = node / n2, bc = node - a * n2;  // [e][a][pair][bc][2]
+    GP[(((e * n + a) * 3 + comp / 2) * n2 + bc) * 2 + (comp & 1)] = G[t];
   }
 }
 

@@ -1,13 +1,12 @@
-// Hexahedral (3-D) operator path of libsem_hip.so: the scatter planner (host,
-// once per map), the per-order launches of sem_hex.h and the 3-D halves of
-// the C ABI entry points (sem_device.hip forwards a context created with
-// ndim = 3 here).  DESIGN.md §4.9 / §5.3.
+// Hexahedral (3-D) operator path of libsem_hip.so: the per-order launches of
+// sem_hex.h and the 3-D halves of the C ABI entry points (sem_device.hip
+// forwards a context created with ndim = 3 here); the scatter plan comes from
+// sem_hex_plan.cpp.  DESIGN.md §4.9 / §5.
 #include <cmath>
 #include <cstdint>
 #include <cstdlib>
 #include <cstring>
-#include <numeric>
-#include <unordered_map>
+#include <type_traits>
 
 #include "sem_ctx.h"
 #include "sem_hex.h"
@@ -94,488 +93,35 @@ int hex_check_order(int n) {
   return SEM_OK;
 }
 
-uint64_t face_hash(const uint32_t* f, int n2) {
-  uint64_t h = 0x9E3779B97F4A7C15ull;
-  for (int j = 0; j < n2; ++j) {
-    h ^= f[j] + 0x9E3779B97F4A7C15ull + (h << 6) + (h >> 2);
-    h *= 0xBF58476D1CE4E5B9ull;
-  }
-  return h ^ (h >> 31);
-}
-
 // ---------------------------------------------------------------------------
-// Planner.  Chains follow xi0: element e' succeeds e when e's face a = n-1 is
-// e''s face a = 0 node for node (same (b, c) order), so one thread holds the
-// shared node row of both.  Chains are cut into sub-chains of <= Lc elements
-// so that the launch has enough workgroups; a workgroup runs S sub-chains of
-// equal length in lockstep (slot s of step k = launch position
-// wg_off + k*S + s).
-//
-// Every (element, node) the kernel writes is a write EVENT, except row
-// a = n-1 of a non-last chain element (carried).  A node with one event is a
-// plain store.  A node with several events is a SEAM node: each of its events
-// goes to a slot of its own and k_hex_seam_sum adds them.  The kernel decides
-// per thread and element from two small masks: a boundary column (b or c on
-// the element boundary) is slotted as a whole when any of its events is on a
-// seam node (cmask bit), a chain's first / last face likewise (cflag).  The
-// planner replays exactly that rule, checks that every plain store hits a
-// one-event node (conforming mesh) and lists the slots of each seam node.
-struct HexPlanHost {
-  std::vector<int> wg_off, wg_len, elist;
-  std::vector<unsigned long long> cmask;
-  std::vector<uint8_t> cflag;
-  std::vector<uint32_t> seam_gid, seam_ptr, seam_idx, zero;
-  int64_t n_slot = 0, face_base = 0, n_chains = 0, n_sub = 0, lc = 0, n_direct = 0;
-};
+// One element kernel: the three-block kernel (action and diagonal), the row
+// form or the matrix-core form (the action only: HEX_SET / HEX_ACC; set_map
+// turns HexState::mfma on only at the orders it is built for), with or
+// without the template map, in the mode asked for
+enum { HEX_FORM_THREE_BLOCK, HEX_FORM_ROWS, HEX_FORM_MFMA };
 
-// hash of an element face given as n^2 entries at f[i * stride1 + j * stride2]
-uint64_t face_hash_strided(const uint32_t* f, int n, int stride1, int stride2) {
-  uint64_t h = 0x9E3779B97F4A7C15ull;
-  for (int i = 0; i < n; ++i)
-    for (int j = 0; j < n; ++j) {
-      h ^= f[i * stride1 + j * stride2] + 0x9E3779B97F4A7C15ull + (h << 6) + (h >> 2);
-      h *= 0xBF58476D1CE4E5B9ull;
-    }
-  return h ^ (h >> 31);
-}
-
-int hex_build_plan(const std::vector<uint32_t>& h, int64_t E, int64_t n_node, int N,
-                   int64_t resident, bool zmerge, bool ymerge, HexPlanHost& P) {
-  const int N2 = N * N;
-  const int64_t N3 = (int64_t)N2 * N;
-  const int S = semh::hex_slots(N), NBC = semh::hex_nbc(N);
-  for (size_t i = 0; i < h.size(); ++i)
-    if (h[i] >= (uint64_t)n_node) return fail(SEM_E_INVALID, "element map entry >= n_node");
-  // 1. successors along xi0
-  std::vector<int64_t> succ(E, -1), pred(E, -1);
-  {
-    std::unordered_map<uint64_t, int64_t> first;
-    first.reserve((size_t)E * 2);
-    for (int64_t e = 0; e < E; ++e) {
-      auto it = first.emplace(face_hash(&h[e * N3], N2), e);
-      if (!it.second) it.first->second = -1;  // ambiguous: never chained
-    }
-    for (int64_t e = 0; e < E; ++e) {
-      const uint32_t* fl = &h[e * N3 + (int64_t)(N - 1) * N2];
-      auto it = first.find(face_hash(fl, N2));
-      if (it == first.end() || it->second < 0 || it->second == e) continue;
-      const int64_t e2 = it->second;
-      if (std::memcmp(fl, &h[e2 * N3], sizeof(uint32_t) * N2) != 0) continue;
-      if (pred[e2] >= 0) continue;
-      succ[e] = e2;
-      pred[e2] = e;
-    }
-  }
-  // 2. maximal chains (heads without predecessor; then any cycle, cut anywhere)
-  std::vector<int64_t> order;
-  std::vector<int64_t> chain_start;
-  order.reserve(E);
-  {
-    std::vector<uint8_t> seen(E, 0);
-    auto walk = [&](int64_t e) {
-      chain_start.push_back((int64_t)order.size());
-      while (e >= 0 && !seen[e]) {
-        seen[e] = 1;
-        order.push_back(e);
-        e = succ[e];
-      }
-    };
-    for (int64_t e = 0; e < E; ++e)
-      if (pred[e] < 0) walk(e);
-    for (int64_t e = 0; e < E; ++e)
-      if (!seen[e]) walk(e);
-    chain_start.push_back((int64_t)order.size());
-  }
-  const int64_t n_chains = (int64_t)chain_start.size() - 1;
-  // 3. sub-chains of near-equal length <= lc.  A workgroup's time grows
-  //    with its sub-chain length and the launch runs in generations of
-  //    `resident` workgroups, so lc minimises generations x sub-chain length
-  //    (ties: the longer sub-chains, fewer seam nodes).  27^3 at p = 8: lc = 9,
-  //    729 workgroups in one generation -- 0.271 against 0.278 ms per step
-  //    for the round's first rule (lc = 3, 2.85 generations) and 0.275 /
-  //    0.288 / 0.305 for lc = 5 / 4 / 7 (profiles/r05/hex/chain_length/).
-  //    A workgroup also pays a fixed start (D into LDS, its flags, the
-  //    first map rows) worth about one element step: cost = generations x
-  //    (sub-chain length + 1).  Without that term the rule took sub-chains
-  //    of one element at p = 1 / 3 / 6 / 7 (~1e7 DOF, many generations
-  //    either way): 1.431 / 0.418 / 0.285 / 0.268 ms per step against 1.193
-  //    / 0.397 / 0.277 / 0.258 with it (sub-chains of 12 / 14 / 8 / 15);
-  //    the other orders keep their plan (profiles/r06/hex_chain_start/).
-  //    SEM_HEX_CHAIN_START sets the term.
-  int64_t lc = 1;
-  {
-    double start = 1.0;
-    if (const char* e = std::getenv("SEM_HEX_CHAIN_START")) start = std::atof(e);
-    double best = 0.0;
-    for (int64_t c = 1; c <= 16; ++c) {
-      int64_t nsub = 0, maxlen = 0;
-      for (int64_t ch = 0; ch < n_chains; ++ch) {
-        const int64_t M = chain_start[ch + 1] - chain_start[ch];
-        const int64_t parts = (M + c - 1) / c;
-        nsub += parts;
-        maxlen = std::max(maxlen, (M + parts - 1) / parts);
-      }
-      const int64_t nwg = (nsub + S - 1) / S;
-      const int64_t gens = resident > 0 ? (nwg + resident - 1) / resident : 1;
-      const double cost = (double)gens * ((double)maxlen + start);
-      if (c == 1 || cost <= best) {
-        best = cost;
-        lc = c;
-      }
-    }
-  }
-  if (const char* s = std::getenv("SEM_HEX_CHAIN")) lc = std::max(1, std::atoi(s));
-  struct Sub {
-    int64_t start, len;
-  };
-  std::vector<Sub> sub;
-  for (int64_t ch = 0; ch < n_chains; ++ch) {
-    const int64_t a0 = chain_start[ch], M = chain_start[ch + 1] - a0;
-    const int64_t parts = (M + lc - 1) / lc;
-    const int64_t q = M / parts, r = M % parts;
-    int64_t off = a0;
-    for (int64_t k = 0; k < parts; ++k) {
-      const int64_t len = q + (k < r ? 1 : 0);
-      sub.push_back({off, len});
-      off += len;
-    }
-  }
-  // 4. longest first, then by the smallest node id of the head element
-  //    (neighbouring sub-chains share faces: on a locality-ordered node
-  //    numbering they run in the same or adjacent workgroups, whatever the
-  //    element order)
-  std::vector<uint32_t> key(sub.size());
-  for (size_t i = 0; i < sub.size(); ++i) {
-    const uint32_t* me = &h[order[sub[i].start] * N3];
-    key[i] = *std::min_element(me, me + N3);
-  }
-  {
-    std::vector<size_t> idx(sub.size());
-    std::iota(idx.begin(), idx.end(), 0);
-    std::stable_sort(idx.begin(), idx.end(), [&](size_t x, size_t y) {
-      if (sub[x].len != sub[y].len) return sub[x].len > sub[y].len;
-      return key[x] < key[y];
-    });
-    std::vector<Sub> sorted(sub.size());
-    for (size_t i = 0; i < idx.size(); ++i) sorted[i] = sub[idx[i]];
-    sub.swap(sorted);
-  }
-  // 5. workgroups of S equal-length sub-chains.  With the y-merge the S
-  //    slots form a GY x GZ grid: row r of a workgroup is GZ sub-chains that
-  //    follow each other along xi2 (xi2 = n-1 face of one = xi2 = 0 face of
-  //    the next at every step), row r + 1 the xi1-neighbours of row r.  A
-  //    workgroup whose first row cannot be completed (mesh edge, irregular
-  //    numbering) takes the next free sub-chains of its length in order, as
-  //    without the y-merge; so does the rest of a grid that ends early.
-  const int GZ = semh::hex_grid_z(N), GY = S / GZ;
-  const bool grid = zmerge && ymerge && GY >= 2;
-  const size_t nsub = sub.size();
-  // same-length neighbour along xi2 (kind 0) / xi1 (kind 1): its face 0
-  // equals my face n-1 at every step
-  auto face_ptr = [&](int64_t e, int kind, int side, int& st1, int& st2) -> const uint32_t* {
-    // kind 0: xi2 face c = side: entries (a, b) at a*N2 + b*N; kind 1: xi1
-    // face b = side: entries (a, c) at a*N2 + c
-    if (kind == 0) {
-      st1 = N2;
-      st2 = N;
-      return &h[e * N3 + side];
-    }
-    st1 = N2;
-    st2 = 1;
-    return &h[e * N3 + (int64_t)side * N];
-  };
-  auto same_faces = [&](int64_t i, int64_t j, int kind) -> bool {
-    if (sub[i].len != sub[j].len) return false;
-    for (int64_t k = 0; k < sub[i].len; ++k) {
-      int a1, a2, b1, b2;
-      const uint32_t* f1 = face_ptr(order[sub[i].start + k], kind, N - 1, a1, a2);
-      const uint32_t* f2 = face_ptr(order[sub[j].start + k], kind, 0, b1, b2);
-      for (int x = 0; x < N; ++x)
-        for (int y = 0; y < N; ++y)
-          if (f1[x * a1 + y * a2] != f2[x * b1 + y * b2]) return false;
-    }
-    return true;
-  };
-  std::vector<int64_t> nbr[2];
-  if (grid)
-    for (int kind = 0; kind < 2; ++kind) {
-      nbr[kind].assign(nsub, -1);
-      std::unordered_map<uint64_t, int64_t> head;
-      head.reserve(nsub * 2);
-      for (size_t j = 0; j < nsub; ++j) {
-        int s1, s2;
-        const uint32_t* f = face_ptr(order[sub[j].start], kind, 0, s1, s2);
-        auto it = head.emplace(face_hash_strided(f, N, s1, s2), (int64_t)j);
-        if (!it.second) it.first->second = -1;  // ambiguous
-      }
-      for (size_t i = 0; i < nsub; ++i) {
-        int s1, s2;
-        const uint32_t* f = face_ptr(order[sub[i].start], kind, N - 1, s1, s2);
-        auto it = head.find(face_hash_strided(f, N, s1, s2));
-        if (it == head.end() || it->second < 0 || it->second == (int64_t)i) continue;
-        if (same_faces((int64_t)i, it->second, kind)) nbr[kind][i] = it->second;
-      }
-    }
-  std::vector<int64_t> sub_wg(nsub, -1), sub_slot(nsub, -1);
-  std::vector<uint8_t> grid_wg;
-  int64_t pos = 0;
-  size_t cur = 0;  // first sub-chain not yet placed
-  std::vector<int64_t> slots(S);
-  while (true) {
-    while (cur < nsub && sub_wg[cur] >= 0) ++cur;
-    if (cur >= nsub) break;
-    const int64_t len = sub[cur].len;
-    const int64_t w = (int64_t)P.wg_off.size();
-    std::fill(slots.begin(), slots.end(), -1);
-    int filled = 0;
-    bool is_grid = false;
-    if (grid) {
-      int64_t rs = (int64_t)cur;
-      for (int r = 0; r < GY && rs >= 0; ++r) {
-        int64_t x = rs;
-        int zi = 0;
-        for (; zi < GZ && x >= 0; ++zi) {
-          bool taken = sub_wg[x] >= 0 || sub[x].len != len;
-          for (int t = 0; t < filled + zi && !taken; ++t) taken = slots[t] == x;
-          if (taken) break;
-          slots[filled + zi] = x;
-          x = zi + 1 < GZ ? nbr[0][x] : x;
-        }
-        if (zi < GZ) {  // incomplete row: drop it
-          for (int t = filled; t < filled + zi; ++t) slots[t] = -1;
-          break;
-        }
-        filled += GZ;
-        rs = nbr[1][slots[filled - GZ]];
-      }
-      is_grid = filled >= 2 * GZ;
-      if (!is_grid) {
-        std::fill(slots.begin(), slots.end(), -1);
-        filled = 0;
-      }
-    }
-    // the rest: the next free sub-chains of this length, in order
-    for (size_t j = cur; j < nsub && filled < S && sub[j].len == len; ++j) {
-      if (sub_wg[j] >= 0) continue;
-      bool taken = false;
-      for (int t = 0; t < filled && !taken; ++t) taken = slots[t] == (int64_t)j;
-      if (!taken) slots[filled++] = (int64_t)j;
-    }
-    if (pos > 0x7FFFFFFFll - len * S) return fail(SEM_E_INVALID, "hex plan: too many elements");
-    P.wg_off.push_back((int)pos);
-    P.wg_len.push_back((int)len);
-    grid_wg.push_back(is_grid ? 1 : 0);
-    for (int64_t k = 0; k < len; ++k)
-      for (int s = 0; s < S; ++s)
-        P.elist.push_back(slots[s] >= 0 ? (int)order[sub[slots[s]].start + k] : -1);
-    for (int s = 0; s < S; ++s)
-      if (slots[s] >= 0) {
-        sub_wg[slots[s]] = w;
-        sub_slot[slots[s]] = s;
-      }
-    pos += len * S;
-  }
-  const int64_t n_wg = (int64_t)P.wg_off.size(), n_pos = pos;
-  P.cmask.assign(n_pos, 0ull);
-  P.cflag.assign(n_wg * S, 0);
-  // 5b. z-merge: slot s of a workgroup hands its xi2 = 0 face to slot s-1
-  //     when, at every chain step, that face IS slot s-1's xi2 = n-1 face
-  //     node for node (same (a, b)); the kernel sums it in LDS.  In a grid
-  //     workgroup only within a row.  y-merge: slot s hands its xi1 = 0 face
-  //     to slot s - GZ likewise (same (a, c)).
-  std::vector<uint8_t> zm(n_wg * S, 0), ym(n_wg * S, 0);
-  auto elem_at = [&](int64_t w, int64_t k, int s) { return P.elist[P.wg_off[w] + k * S + s]; };
-  if (zmerge)
-    for (int64_t w = 0; w < n_wg; ++w)
-      for (int s = 1; s < S; ++s) {
-        if (grid_wg[w] && s % GZ == 0) continue;
-        bool ok = true;
-        for (int64_t k = 0; k < P.wg_len[w] && ok; ++k) {
-          const int e1 = elem_at(w, k, s - 1), e2 = elem_at(w, k, s);
-          if (e1 < 0 || e2 < 0) {
-            ok = false;
-            break;
-          }
-          const uint32_t* m1 = &h[(int64_t)e1 * N3];
-          const uint32_t* m2 = &h[(int64_t)e2 * N3];
-          for (int ab = 0; ab < N2 && ok; ++ab) ok = m1[ab * N + N - 1] == m2[ab * N];
-        }
-        zm[w * S + s] = ok ? 1 : 0;
-      }
-  if (grid)
-    for (int64_t w = 0; w < n_wg; ++w) {
-      if (!grid_wg[w]) continue;
-      for (int s = GZ; s < S; ++s) {
-        bool ok = true;
-        for (int64_t k = 0; k < P.wg_len[w] && ok; ++k) {
-          const int e1 = elem_at(w, k, s - GZ), e2 = elem_at(w, k, s);
-          if (e1 < 0 || e2 < 0) {
-            ok = false;
-            break;
-          }
-          const uint32_t* m1 = &h[(int64_t)e1 * N3];
-          const uint32_t* m2 = &h[(int64_t)e2 * N3];
-          for (int a = 0; a < N && ok; ++a)
-            for (int c = 0; c < N && ok; ++c) ok = m1[a * N2 + (N - 1) * N + c] == m2[a * N2 + c];
-        }
-        ym[w * S + s] = ok ? 1 : 0;
-      }
-    }
-  // a thread whose column is handed over emits no write of its own (the
-  // kernel's give / ygive, sem_hex.h)
-  auto merged = [&](int64_t w, int64_t s, int b, int c) {
-    if (c == 0 && zm[w * S + s]) return true;
-    return b == 0 && ym[w * S + s] && !(c == 0 && zm[w * S + s - GZ]);
-  };
-  // 6. events per node
-  std::vector<uint8_t> cnt(n_node, 0);
-  auto bump = [&](uint32_t g) {
-    if (cnt[g] < 255) ++cnt[g];
-  };
-  for (size_t i = 0; i < sub.size(); ++i) {
-    const int64_t len = sub[i].len;
-    for (int64_t k = 0; k < len; ++k) {
-      const uint32_t* me = &h[order[sub[i].start + k] * N3];
-      const int amax = (k == len - 1) ? N : N - 1;
-      for (int64_t t = 0; t < (int64_t)amax * N2; ++t)
-        if (!merged(sub_wg[i], sub_slot[i], (int)((t / N) % N), (int)(t % N))) bump(me[t]);
-    }
-  }
-  // 7. face flags, column masks
-  auto bcol_of = [&](int b, int c) -> int {
-    if (b == 0) return c;
-    if (b == N - 1) return 3 * N - 4 + c;
-    if (c == 0) return N + 2 * (b - 1);
-    if (c == N - 1) return N + 2 * (b - 1) + 1;
-    return -1;
-  };
-  for (size_t i = 0; i < sub.size(); ++i) {
-    const int64_t len = sub[i].len;
-    const uint32_t* hd = &h[order[sub[i].start] * N3];
-    const uint32_t* tl = &h[order[sub[i].start + len - 1] * N3 + (int64_t)(N - 1) * N2];
-    uint8_t f = 0;
-    for (int j = 0; j < N2; ++j) {
-      if (cnt[hd[j]] > 1) f |= 1;
-      if (cnt[tl[j]] > 1) f |= 2;
-    }
-    if (zm[sub_wg[i] * S + sub_slot[i]]) f |= 4;
-    if (ym[sub_wg[i] * S + sub_slot[i]]) f |= 8;
-    P.cflag[sub_wg[i] * S + sub_slot[i]] = f;
-    for (int64_t k = 0; k < len; ++k) {
-      const int64_t p = P.wg_off[sub_wg[i]] + k * S + sub_slot[i];
-      const uint32_t* me = &h[order[sub[i].start + k] * N3];
-      unsigned long long mask = 0;
-      for (int b = 0; b < N; ++b)
-        for (int c = 0; c < N; ++c) {
-          const int bcol = bcol_of(b, c);
-          if (bcol < 0 || merged(sub_wg[i], sub_slot[i], b, c)) continue;
-          for (int a = 0; a < N; ++a) {
-            if (a == N - 1 && k < len - 1) continue;
-            if (a == 0 && k == 0 && (f & 1)) continue;
-            if (a == N - 1 && k == len - 1 && (f & 2)) continue;
-            if (cnt[me[a * N2 + b * N + c]] > 1) {
-              mask |= 1ull << bcol;
-              break;
-            }
-          }
-        }
-      P.cmask[p] = mask;
-    }
-  }
-  // 8. replay the kernel's rule: plain stores must hit one-event nodes; the
-  //    slotted events of each seam node, in a fixed order (counting sort)
-  P.face_base = n_pos * N * NBC;
-  P.n_slot = P.face_base + n_wg * S * 2 * N2;
-  if (P.n_slot >= 0xFFFFFFFFll) return fail(SEM_E_INVALID, "hex plan: slot space exceeds 2^32");
-  std::vector<uint32_t> scount(n_node + 1, 0);
-  int64_t n_direct = 0;
-  auto for_events = [&](auto&& fn) -> int {
-    for (size_t i = 0; i < sub.size(); ++i) {
-      const int64_t len = sub[i].len, w = sub_wg[i], s = sub_slot[i];
-      const uint8_t f = P.cflag[w * S + s];
-      for (int64_t k = 0; k < len; ++k) {
-        const int64_t p = P.wg_off[w] + k * S + s;
-        const uint32_t* me = &h[order[sub[i].start + k] * N3];
-        const unsigned long long mask = P.cmask[p];
-        for (int b = 0; b < N; ++b)
-          for (int c = 0; c < N; ++c) {
-            const int bc = b * N + c, bcol = bcol_of(b, c);
-            if (merged(w, s, b, c)) continue;
-            const bool colslot = bcol >= 0 && ((mask >> bcol) & 1ull);
-            for (int a = 0; a < N; ++a) {
-              if (a == N - 1 && k < len - 1) continue;
-              const uint32_t g = me[a * N2 + bc];
-              int64_t sidx = -1;
-              if (a == 0 && k == 0 && (f & 1))
-                sidx = P.face_base + (w * S + s) * 2 * N2 + bc;
-              else if (a == N - 1 && k == len - 1 && (f & 2))
-                sidx = P.face_base + (w * S + s) * 2 * N2 + N2 + bc;
-              else if (colslot)
-                sidx = (p * N + a) * NBC + bcol;
-              if (int rc = fn(g, sidx, (int64_t)i)) return rc;
-            }
-          }
-      }
-    }
-    return SEM_OK;
-  };
-  int rc = for_events([&](uint32_t g, int64_t sidx, int64_t) -> int {
-    if (sidx < 0) {
-      if (cnt[g] != 1)
-        return fail(SEM_E_NOTIMPL,
-                    "hex plan: a node inside an element column is shared (non-conforming mesh)");
-      ++n_direct;
-    } else {
-      ++scount[g];
-    }
-    return SEM_OK;
-  });
-  if (rc) return rc;
-  std::vector<uint32_t> start(n_node + 1, 0);
-  for (int64_t g = 0; g < n_node; ++g) start[g + 1] = start[g] + scount[g];
-  const uint32_t n_writes = start[n_node];
-  P.seam_idx.assign(n_writes, 0);
-  std::vector<uint32_t> fill(start.begin(), start.end() - 1);
-  for_events([&](uint32_t g, int64_t sidx, int64_t) -> int {
-    if (sidx >= 0) P.seam_idx[fill[g]++] = (uint32_t)sidx;
-    return SEM_OK;
-  });
-  P.seam_ptr.push_back(0);
-  for (int64_t g = 0; g < n_node; ++g) {
-    if (scount[g]) {
-      P.seam_gid.push_back((uint32_t)g);
-      P.seam_ptr.push_back(start[g + 1]);
-    }
-    if (cnt[g] == 0) P.zero.push_back((uint32_t)g);
-  }
-  P.n_chains = n_chains;
-  P.n_sub = (int64_t)sub.size();
-  P.lc = lc;
-  P.n_direct = n_direct;
-  return SEM_OK;
-}
-
-// ---------------------------------------------------------------------------
-// the matrix-core form of the action (HEX_SET / HEX_ACC; set_map turns
-// HexState::mfma on only at the orders it is built for)
-template <int N>
-void launch_hex_mfma(const HexState* H, const semh::HexLaunch& L, int mode, const double* u,
-                     double* y, const double* d_D, hipStream_t st) {
-  if constexpr (N >= semh::HEX_MFMA_MIN_N && N <= semh::HEX_MFMA_MAX_N) {
-    const dim3 g((unsigned)H->n_wg), b(semh::hex_threads(N));
-    if (H->tmap && mode == semh::HEX_SET)
-      hipLaunchKernelGGL((semh::k_hex_mfma<N, semh::HEX_SET, true>), g, b, 0, st, u, y, H->d_map,
-                         H->d_G, d_D, L);
-    else if (H->tmap)
-      hipLaunchKernelGGL((semh::k_hex_mfma<N, semh::HEX_ACC, true>), g, b, 0, st, u, y, H->d_map,
-                         H->d_G, d_D, L);
-    else if (mode == semh::HEX_SET)
-      hipLaunchKernelGGL((semh::k_hex_mfma<N, semh::HEX_SET>), g, b, 0, st, u, y, H->d_map,
-                         H->d_G, d_D, L);
+template <int N, int FORM, bool TM>
+void launch_hex_form(const HexState* H, const semh::HexLaunch& L, int mode, const double* u,
+                     double* y, const double* d_D, const semh::HexD<N>& Dk, hipStream_t st) {
+  const dim3 g((unsigned)H->n_wg), b(semh::hex_threads(N));
+  auto launch = [&](auto mode_c) {
+    constexpr int MODE = decltype(mode_c)::value;
+    if constexpr (FORM == HEX_FORM_MFMA)
+      hipLaunchKernelGGL((semh::k_hex_mfma<N, MODE, TM>), g, b, 0, st, u, y, H->d_map, H->d_G, d_D,
+                         L);
+    else if constexpr (FORM == HEX_FORM_ROWS)
+      hipLaunchKernelGGL((semh::k_hex_rows<N, MODE, TM>), g, b, 0, st, u, y, H->d_map, H->d_G, d_D,
+                         L, Dk);
     else
-      hipLaunchKernelGGL((semh::k_hex_mfma<N, semh::HEX_ACC>), g, b, 0, st, u, y, H->d_map,
-                         H->d_G, d_D, L);
-  }
+      hipLaunchKernelGGL((semh::k_hex_poisson<N, MODE, TM>), g, b, 0, st, u, y, H->d_map, H->d_G,
+                         d_D, L, Dk);
+  };
+  if (mode == semh::HEX_SET)
+    launch(std::integral_constant<int, semh::HEX_SET>{});
+  else if (mode == semh::HEX_ACC)
+    launch(std::integral_constant<int, semh::HEX_ACC>{});
+  else if constexpr (FORM == HEX_FORM_THREE_BLOCK)
+    launch(std::integral_constant<int, semh::HEX_DIAG>{});
 }
 
 template <int N>
@@ -583,41 +129,27 @@ int launch_hex_apply(sem_ctx* c, int mode, const double* u, double* y, hipStream
   HexState* H = c->hex;
   const semh::HexLaunch L{H->d_wg_off, H->d_wg_len, H->d_elist,   H->d_cmask,
                           H->d_cflag,  H->d_slot,   H->face_base, H->d_ebase, H->d_tmpl};
-  const dim3 g((unsigned)H->n_wg), b(semh::hex_threads(N));
   semh::HexD<N> Dk;
   for (int i = 0; i < N * N; ++i) Dk.d[i] = c->hD[i];
-  if (H->mfma && mode != semh::HEX_DIAG)
-    launch_hex_mfma<N>(H, L, mode, u, y, c->d_D, st);
-  else if (H->rows && H->tmap && mode == semh::HEX_SET)
-    hipLaunchKernelGGL((semh::k_hex_rows<N, semh::HEX_SET, true>), g, b, 0, st, u, y, H->d_map,
-                       H->d_G, c->d_D, L, Dk);
-  else if (H->rows && H->tmap && mode == semh::HEX_ACC)
-    hipLaunchKernelGGL((semh::k_hex_rows<N, semh::HEX_ACC, true>), g, b, 0, st, u, y, H->d_map,
-                       H->d_G, c->d_D, L, Dk);
-  else if (H->rows && mode == semh::HEX_SET)
-    hipLaunchKernelGGL((semh::k_hex_rows<N, semh::HEX_SET>), g, b, 0, st, u, y, H->d_map, H->d_G,
-                       c->d_D, L, Dk);
-  else if (H->rows && mode == semh::HEX_ACC)
-    hipLaunchKernelGGL((semh::k_hex_rows<N, semh::HEX_ACC>), g, b, 0, st, u, y, H->d_map, H->d_G,
-                       c->d_D, L, Dk);
-  else if (H->tmap && mode == semh::HEX_SET)
-    hipLaunchKernelGGL((semh::k_hex_poisson<N, semh::HEX_SET, true>), g, b, 0, st, u, y,
-                       H->d_map, H->d_G, c->d_D, L, Dk);
-  else if (H->tmap && mode == semh::HEX_ACC)
-    hipLaunchKernelGGL((semh::k_hex_poisson<N, semh::HEX_ACC, true>), g, b, 0, st, u, y,
-                       H->d_map, H->d_G, c->d_D, L, Dk);
-  else if (H->tmap)
-    hipLaunchKernelGGL((semh::k_hex_poisson<N, semh::HEX_DIAG, true>), g, b, 0, st, u, y,
-                       H->d_map, H->d_G, c->d_D, L, Dk);
-  else if (mode == semh::HEX_SET)
-    hipLaunchKernelGGL((semh::k_hex_poisson<N, semh::HEX_SET>), g, b, 0, st, u, y, H->d_map,
-                       H->d_G, c->d_D, L, Dk);
-  else if (mode == semh::HEX_ACC)
-    hipLaunchKernelGGL((semh::k_hex_poisson<N, semh::HEX_ACC>), g, b, 0, st, u, y, H->d_map,
-                       H->d_G, c->d_D, L, Dk);
-  else
-    hipLaunchKernelGGL((semh::k_hex_poisson<N, semh::HEX_DIAG>), g, b, 0, st, u, y, H->d_map,
-                       H->d_G, c->d_D, L, Dk);
+  const bool action = mode != semh::HEX_DIAG;  // the diagonal always runs k_hex_poisson
+  if (H->mfma && action) {
+    if constexpr (N >= semh::HEX_MFMA_MIN_N && N <= semh::HEX_MFMA_MAX_N) {
+      if (H->tmap)
+        launch_hex_form<N, HEX_FORM_MFMA, true>(H, L, mode, u, y, c->d_D, Dk, st);
+      else
+        launch_hex_form<N, HEX_FORM_MFMA, false>(H, L, mode, u, y, c->d_D, Dk, st);
+    }
+  } else if (H->rows && action) {
+    if (H->tmap)
+      launch_hex_form<N, HEX_FORM_ROWS, true>(H, L, mode, u, y, c->d_D, Dk, st);
+    else
+      launch_hex_form<N, HEX_FORM_ROWS, false>(H, L, mode, u, y, c->d_D, Dk, st);
+  } else {
+    if (H->tmap)
+      launch_hex_form<N, HEX_FORM_THREE_BLOCK, true>(H, L, mode, u, y, c->d_D, Dk, st);
+    else
+      launch_hex_form<N, HEX_FORM_THREE_BLOCK, false>(H, L, mode, u, y, c->d_D, Dk, st);
+  }
   HIP_TRY(hipGetLastError());
   if (H->n_seam) {
     const dim3 gs(grid_for(H->n_seam, 256, 8192)), bs(256);
@@ -813,7 +345,7 @@ int ctx_init(sem_ctx* c) {
   const char* re = std::getenv("SEM_HEX_ROWS");
   c->hex->rows = re ? std::atoi(re) != 0 : hex_rows_default(c->n);
   const char* ze = std::getenv("SEM_HEX_ZMERGE");
-  c->hex->zmerge = HEX_ZMERGE && !(ze && std::atoi(ze) == 0);
+  c->hex->zmerge = !(ze && std::atoi(ze) == 0);
   // y-merge by default at n <= 4 (p <= 3), where it measured faster (p = 1 /
   // 2 / 3: 1.530 -> 1.429, 0.589 -> 0.544, 0.430 -> 0.415 ms per step at
   // ~1e7 DOF); at p = 4 / 7 its extra barrier per step outweighs the seams
@@ -853,35 +385,21 @@ int set_map(sem_ctx* c, const uint32_t* d_e2n, hipStream_t st) {
   // the matrix-core form on request, where it is built (other orders stay
   // on the column forms: SEM_KERNEL=1 in the environment reaches every context)
   const bool mfma = c->kernel == SEM_KERNEL_MFMA && N >= HEX_MFMA_MIN_N && N <= HEX_MFMA_MAX_N;
-  // template map (HexLaunch::ebase / tmpl): does every element's map equal
-  // its first node's id + the offsets of element 0?
-  std::vector<int> tmpl((size_t)N3);
+  // template map (HexLaunch::ebase / tmpl; SEM_HEX_TMAP=0 turns it off)
+  std::vector<int> tmpl;
   std::vector<uint32_t> eb;
-  bool tmap_ok;
-  {
-    const char* te = std::getenv("SEM_HEX_TMAP");
-    bool ok = c->n_elem > 0 && !(te && std::atoi(te) == 0);
-    if (ok) {
-      for (int64_t i = 0; i < N3 && ok; ++i) {
-        const int64_t d = (int64_t)h[i] - (int64_t)h[0];
-        ok = d >= INT32_MIN && d <= INT32_MAX;
-        tmpl[(size_t)i] = (int)d;
-      }
-      eb.resize((size_t)c->n_elem);
-      for (int64_t e = 0; e < c->n_elem && ok; ++e) {
-        const uint32_t* me = &h[(size_t)e * N3];
-        eb[(size_t)e] = me[0];
-        for (int64_t i = 1; i < N3 && ok; ++i) ok = me[i] == me[0] + (uint32_t)tmpl[(size_t)i];
-      }
-    }
-    tmap_ok = ok;
-  }
+  const char* te = std::getenv("SEM_HEX_TMAP");
+  const bool tmap_ok =
+      !(te && std::atoi(te) == 0) && semhexplan::hex_template_map(h, c->n_elem, N, tmpl, eb);
   int wpc = 0, rc = SEM_OK;
   HEX_DISPATCH(rc, N, hex_wgs_per_cu, H->rows, mfma, tmap_ok, &wpc);
   if (rc) return rc;
-  const int64_t resident = (int64_t)std::max(c->n_cu, 1) * std::max(wpc, 1);
-  HexPlanHost P;
-  rc = hex_build_plan(h, c->n_elem, c->n_node, N, resident, H->zmerge, H->ymerge, P);
+  semhexplan::HexPlanOptions opt = semhexplan::hex_plan_options_from_env();
+  opt.zmerge = H->zmerge;
+  opt.ymerge = H->ymerge;
+  opt.resident = (int64_t)std::max(c->n_cu, 1) * std::max(wpc, 1);
+  semhexplan::HexPlan P;
+  rc = semhexplan::hex_plan_map(h, c->n_elem, c->n_node, N, opt, P);
   if (rc) return rc;
   c->epoch++;
   c->map_epoch++;

@@ -49,16 +49,6 @@ typedef double hdbl4 __attribute__((ext_vector_type(4)));
 
 constexpr int HEX_MFMA_MIN_N = 12;
 constexpr int HEX_MFMA_MAX_N = 17;
-// the thread's map entries held in registers across an element step (and the
-// next element's loaded one step ahead, as k_hex_rows does) or read twice:
-// 17-34 registers that decide between two and three, or three and four,
-// waves per SIMD.  Off measured 13 % faster at p = 12 and p = 16, 3 % slower
-// at p = 15; -DSEM_HEX_MFMA_MAPREG=1 builds the other form
-#ifndef SEM_HEX_MFMA_MAPREG
-#define SEM_HEX_MFMA_MAPREG 0
-#endif
-constexpr bool HEX_MFMA_MAPREG = SEM_HEX_MFMA_MAPREG != 0;
-
 constexpr int hex_mfma_sa(int n) {
   int s = n * n;
   while (s % 8 != 4) ++s;
@@ -95,7 +85,7 @@ __global__ void __launch_bounds__(hex_threads(N), hex_mfma_min_waves(N))
   constexpr int NT = (N + 15) / 16;  // tiles per index
   constexpr int KS = (N + 3) / 4;    // k-steps
   constexpr int SA = hex_mfma_sa(N);
-  constexpr int GROW = 3 * N2, GPAIR = HEX_GSOA ? N2 : 1;  // factor layout (hex_g)
+  constexpr int GROW = 3 * N2, GPAIR = N2;  // factor layout (hex_g)
   __shared__ double sU[N * SA];  // u, then w2, then y: [a][b][c] at a * SA + b * N + c
   __shared__ double sX[N3];      // d1, then w1:        [a][b][c] at a * N2 + b * N + c
   const int tid = threadIdx.x;
@@ -123,8 +113,10 @@ __global__ void __launch_bounds__(hex_threads(N), hex_mfma_min_waves(N))
   const bool active = tid < N2;
   const int bc = active ? tid : 0;
   const int b_ = bc / N, c_ = bc - b_ * N;
-  const int bcol = hex_bcol<N>(b_, c_);
+  static_assert(hex_bcol_agrees<N>(), "hex_bcol_n differs from hex_bcol");
+  const int bcol = hex_bcol_n<N>(b_, c_);
   const uint8_t cf = P.cflag[w];
+  // hex_face_slot(N, P.face_base, w, 0, 0, bc); the tail face N2 further
   double* const face = P.slot + P.face_base + (int64_t)w * 2 * N2 + bc;
   double carry = 0.0;
   int en = P.elist[base];
@@ -143,26 +135,19 @@ __global__ void __launch_bounds__(hex_threads(N), hex_mfma_min_waves(N))
       for (int a = 0; a < N; ++a) dst[a] = map[(int64_t)el * N3 + a * N2 + bc];
     }
   };
-  // MAPREG: the column's map entries stay in registers from the gather to
-  // the stores and the next element's are loaded one step ahead, as in
-  // k_hex_rows; otherwise they are read again for the stores (n registers
-  // fewer across the products)
-  constexpr bool MAPREG = HEX_MFMA_MAPREG;
-  [[maybe_unused]] uint32_t mn[MAPREG ? N : 1];
-  if constexpr (MAPREG)
-    if (active) load_map(en, mn);
+  // The map entries are read twice per element step, for the gather and
+  // again for the stores, instead of staying in registers across the
+  // products with the next element's loaded one step ahead, as k_hex_rows
+  // does: 17-34 registers that decide between two and three, or three and
+  // four, waves per SIMD.  Reading twice measured 13 % faster at p = 12 and
+  // p = 16, 3 % slower at p = 15.
   const hdbl4 z = {0.0, 0.0, 0.0, 0.0};
 #pragma unroll 1
   for (int k = 0; k < L; ++k) {
     const int pos = base + k;
     const int e = en;
     uint32_t m[N];
-    if constexpr (MAPREG) {
-#pragma unroll
-      for (int a = 0; a < N; ++a) m[a] = mn[a];
-    } else {
-      if (active) load_map(e, m);
-    }
+    if (active) load_map(e, m);
     if (active) {
       double uc[N];
 #pragma unroll
@@ -171,11 +156,7 @@ __global__ void __launch_bounds__(hex_threads(N), hex_mfma_min_waves(N))
       for (int a = 0; a < N; ++a) sU[a * SA + bc] = uc[a];
     }
     __syncthreads();  // u complete; the previous element's sX reads are done
-    if (k + 1 < L) {
-      en = P.elist[pos + 1];
-      if constexpr (MAPREG)
-        if (active) load_map(en, mn);
-    }
+    if (k + 1 < L) en = P.elist[pos + 1];
     // phase A: d1[a, b, c] = sum_r D[b][r] U[a, r, c], tiles (b, c) at fixed a
 #pragma unroll 1
     for (int a = wave; a < N; a += NW) {
@@ -348,9 +329,10 @@ __global__ void __launch_bounds__(hex_threads(N), hex_mfma_min_waves(N))
       }
     }
     __syncthreads();  // y complete
-    // the write rule of k_hex_rows, thread (b, c): its column of y
+    // the write rule of k_hex_rows (sem_hex_plan.cpp thread_rows), thread (b, c):
+    // its column of y
     if (active) {
-      if constexpr (!MAPREG) load_map(e, m);
+      load_map(e, m);
       double yv[N];
 #pragma unroll
       for (int a = 0; a < N; ++a) yv[a] = sU[a * SA + bc];  // rewritten by this thread only
@@ -363,9 +345,9 @@ __global__ void __launch_bounds__(hex_threads(N), hex_mfma_min_waves(N))
       for (int a = 0; a < N; ++a) {
         if (a == N - 1 && !last) continue;  // carried into the next element's row 0
         const double v = yv[a];
-        if (a == 0 && k == 0 && (cf & 1)) {
+        if (a == 0 && k == 0 && (cf & HEX_CF_HEAD)) {
           face[0] = v;
-        } else if (a == N - 1 && last && (cf & 2)) {
+        } else if (a == N - 1 && last && (cf & HEX_CF_TAIL)) {
           face[N2] = v;
         } else if (colslot) {
           cs[a * NBC] = v;

@@ -85,7 +85,7 @@ class SlabPartition(object):
     self._mesh.cells`` (sem/discrete.py:189-209) over its N-D tensor layer
     (sem/basis_functions.py:626-650).  The hexahedral chains run along xi0 =
     x, so a slab of L layers gives chains of L elements (the planner cuts
-    longer ones anyway, csrc/sem_hex.hip hex_build_plan)."""
+    longer ones anyway, csrc/sem_hex_plan.cpp hex_plan_map)."""
 
     def __init__(self, nex, ney, nez, p, world, rank):
         if world < 1 or not (0 <= rank < world):

@@ -20,6 +20,7 @@ import numpy as np
 import pytest
 
 from conftest import rel_l2
+from hex_meshes import permute_local
 
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
@@ -228,25 +229,6 @@ def test_hex_template_map_bitwise(sem, monkeypatch, p, rows):
     assert not op.plan_info()["template_map"]
 
 
-def _permute_local(e2n, rng, frac=0.5):
-    """Re-orient a fraction of the elements (swap / reverse local axes): the
-    mesh is the same, the xi0 chains break wherever orientations differ."""
-    e2n = e2n.copy()
-    for e in np.flatnonzero(rng.random(e2n.shape[0]) < frac):
-        perm = rng.permutation(3)
-        flips = rng.random(3) < 0.5
-        # orientation-preserving only (a reflection would make detJ < 0)
-        sign = np.linalg.det(np.eye(3)[perm]) * (-1) ** int(flips.sum())
-        if sign < 0:
-            flips[0] = not flips[0]
-        t = np.transpose(e2n[e], perm)
-        for ax in range(3):
-            if flips[ax]:
-                t = np.flip(t, axis=ax)
-        e2n[e] = t
-    return e2n
-
-
 @pytest.mark.parametrize("case", ["shuffle_elements", "shuffle_nodes", "reoriented",
                                   "reoriented_shuffled"])
 def test_hex_broken_chains_vs_oracle(sem, gll, case):
@@ -260,7 +242,7 @@ def test_hex_broken_chains_vs_oracle(sem, gll, case):
     if case == "shuffle_nodes":
         nodes, e2n = meshgen.shuffle_nodes(nodes, e2n, seed=4)
     if case.startswith("reoriented"):
-        e2n = _permute_local(e2n, rng)
+        e2n = permute_local(e2n, rng)
     P = _oracle(gll, nodes, e2n, p)
     op = sem.SEMOperator(p, e2n, nodes)
     u = rng.standard_normal(P.ndof)
