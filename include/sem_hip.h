@@ -764,6 +764,73 @@ int sem_faces_assemble(sem_faces* faces, const double* d_vals, double* d_out, in
 int sem_faces_info(sem_faces* faces, int64_t* info, int n_info);
 
 /* ------------------------------------------------------------------ */
+/* Transfer: fields between two polynomial orders of one mesh           */
+/* ------------------------------------------------------------------ */
+/* Two discretisations "from" and "to" of the same elements: the same n_elem
+ * and element order, the same local axis orientation per element, maps
+ * e2n_from uint32 [n_elem][n_from^ndim] and e2n_to [n_elem][n_to^ndim]
+ * (n = p + 1).  Quadrilaterals and hexahedra, any 1 <= p_from, p_to <= 16 in
+ * either direction; p_from > p_to is nodal interpolation down, p_from == p_to
+ * a renumbering copy.  The reference has no counterpart.
+ *
+ * J [n_to][n_from], J[i][j] = l_j^from(x_i^to): the order-p_from GLL Lagrange
+ * basis at the order-p_to GLL nodes (sem_gll_table, sem_lagrange_eval: a
+ * coincident node gives exactly 0 or 1).
+ *   - prolong: u_to[g] = ((J x J [x J]) u_from[e2n_from[e]])[l] for the owner
+ *     (e, l) of the "to" node g, the lowest (element, local index) pair that
+ *     references g.  On a conforming input every referencing element gives
+ *     the same value up to rounding; the owner rule makes the result bitwise
+ *     repeatable.  "To" nodes no element references are left untouched.
+ *   - restrict: r_from = P^T r_to, the exact transpose of that matrix P: per
+ *     element r_to at its owned entries (zero elsewhere) times Jt x Jt [x Jt],
+ *     summed into the "from" nodes in ascending (element, local index) order
+ *     per node, without atomics: bitwise repeatable.
+ * Vectors are read and written as v[c * comp_stride + node * node_stride]
+ * (sem_points_eval's strides), c < ncomp <= 65535. */
+typedef struct sem_transfer sem_transfer;
+
+/* d_e2n_from / d_e2n_to: the two device maps, BORROWED until
+ * sem_transfer_destroy: the kernels read them at every call, the caller keeps
+ * them allocated and unchanged.  They are copied to the host once, where
+ * every id is checked before any launch and the plan is made (the owner mask
+ * of the "to" map, the CSR of the (element, local) entries of every "from"
+ * node): SEM_E_INVALID for ndim not 2 or 3, an order < 1, n_elem < 0 (0 is
+ * valid), a node count outside [0, 2^32], n_elem * n^ndim >= 2^31 on either
+ * side, a NULL map, an id >= its n_node; SEM_E_NOTIMPL for an order > 16.
+ * The handle owns a scratch of 2 * n_elem * n_from^ndim doubles for restrict.
+ * Synchronises `stream`. */
+int sem_transfer_create(sem_transfer** out, int ndim, int p_from, int p_to, int64_t n_elem,
+                        const uint32_t* d_e2n_from, int64_t n_node_from,
+                        const uint32_t* d_e2n_to, int64_t n_node_to, int device, void* stream);
+void sem_transfer_destroy(sem_transfer* transfer);
+
+/* d_u_to = P d_u_from.  d_u_from holds n_node_from nodes per component,
+ * d_u_to n_node_to (the caller's obligation, as in sem_points_eval;
+ * transfer.Transfer refuses any other size).  One launch; allocates nothing
+ * and does not synchronise (graph-capturable).  SEM_E_INVALID for a NULL
+ * handle or array, ncomp outside [1, 65535], a stride < 0 / < 1. */
+int sem_transfer_prolong(sem_transfer* transfer, int ncomp, int64_t comp_stride_from,
+                         int64_t node_stride_from, const double* d_u_from,
+                         int64_t comp_stride_to, int64_t node_stride_to, double* d_u_to,
+                         void* stream);
+
+/* d_r_from (+)= P^T d_r_to.  Overwrite mode (accumulate = 0) writes every
+ * "from" node, 0 where no element references it; accumulate != 0 adds to
+ * d_r_from and leaves such nodes alone.  Two launches per two components
+ * (element kernel into the handle's scratch, then one thread per "from" node
+ * over its CSR row); allocates nothing and does not synchronise.  Calls on
+ * one handle must be ordered (one stream, or events): they share the scratch. */
+int sem_transfer_restrict(sem_transfer* transfer, int ncomp, int64_t comp_stride_to,
+                          int64_t node_stride_to, const double* d_r_to,
+                          int64_t comp_stride_from, int64_t node_stride_from, double* d_r_from,
+                          int accumulate, void* stream);
+
+/* info[0] ndim, [1] p_from, [2] p_to, [3] elements, [4] / [5] "from" / "to"
+ * node counts, [6] owned "to" entries (= referenced "to" nodes), [7] longest
+ * CSR row of a "from" node, [8] scratch bytes.  Writes min(n_info, 9) values. */
+int sem_transfer_info(sem_transfer* transfer, int64_t* info, int n_info);
+
+/* ------------------------------------------------------------------ */
 /* Element matrices: the dense local systems of the assembled path      */
 /* ------------------------------------------------------------------ */
 /* The dense element operators the reference builds per element in Python --

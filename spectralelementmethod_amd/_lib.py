@@ -123,6 +123,13 @@ SIGNATURES = {
     "sem_faces_flux": (C.c_int, [_vp, _vp, C.c_int, _i64, _i64, _vp, _vp, _vp, _vp]),
     "sem_faces_assemble": (C.c_int, [_vp, _vp, _vp, _i64, C.c_int, _vp]),
     "sem_faces_info": (C.c_int, [_vp, C.POINTER(_i64), C.c_int]),
+    "sem_transfer_create": (C.c_int, [C.POINTER(_vp), C.c_int, C.c_int, C.c_int, _i64, _vp, _i64,
+                                      _vp, _i64, C.c_int, _vp]),
+    "sem_transfer_destroy": (None, [_vp]),
+    "sem_transfer_prolong": (C.c_int, [_vp, C.c_int, _i64, _i64, _vp, _i64, _i64, _vp, _vp]),
+    "sem_transfer_restrict": (C.c_int, [_vp, C.c_int, _i64, _i64, _vp, _i64, _i64, _vp, C.c_int,
+                                        _vp]),
+    "sem_transfer_info": (C.c_int, [_vp, C.POINTER(_i64), C.c_int]),
     "sem_elem_matrices": (C.c_int, [C.c_int, C.c_int, C.c_int, _i64, _vp, _dp, _dp, C.c_double,
                                     _vp, _vp, C.POINTER(C.c_int32), _i64, _i64, _vp, _vp, _vp]),
 }

@@ -588,6 +588,12 @@ class DOFManager(object):
                 fe_parent = FiniteElement(self, self._mesh.get_cell(i), compute_flags, i)
             yield fe_parent, SubFiniteElement(fe_parent, int(face[k]), host, k)
 
+    def transfer_to(self, other_dm, check=True):
+        """``SEMOperator.transfer_to`` of the two managers' operators: the
+        device transfer of coefficient vectors from this manager's mesh and
+        order to ``other_dm``'s (same cells in the same order)."""
+        return self.operator().transfer_to(other_dm.operator(), check=check)
+
     def values_at_nodes(self, coeffs):
         """Values at the equispaced element nodes (sem/discrete.py:235-258),
         all cells in one device launch."""

@@ -364,6 +364,18 @@ class SEMOperator(object):
         from .faces import FaceSet
         return FaceSet(self, elem, face)
 
+    def transfer_to(self, other, check=True):
+        """The ``transfer.Transfer`` from this operator's discretisation to
+        ``other``'s, an operator of any order 1..16 on the same elements in
+        the same order with the same local axes (another order, or another
+        node numbering): ``prolong`` carries coefficient vectors over,
+        ``restrict`` is its exact transpose.  It keeps both operators alive.
+        ``check`` compares the corner coordinates of every element of the two
+        meshes on the host and raises ValueError when elements or
+        orientations do not correspond."""
+        from .transfer import between
+        return between(self, other, check=check)
+
     # ------------------------------------------------------------------
     def _vec(self, v, name):
         if not isinstance(v, torch.Tensor):
