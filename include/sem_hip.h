@@ -831,6 +831,103 @@ int sem_transfer_restrict(sem_transfer* transfer, int ncomp, int64_t comp_stride
 int sem_transfer_info(sem_transfer* transfer, int64_t* info, int n_info);
 
 /* ------------------------------------------------------------------ */
+/* Volume: gradients, recovery, integrals, norms, lumped mass           */
+/* ------------------------------------------------------------------ */
+/* The batched device form of FiniteElement.gradient / deriv / integrate
+ * (sem/discrete.py:674-689), which the reference runs per element in NumPy,
+ * plus what convergence studies build from them: the continuous nodal
+ * gradient, the GLL-quadrature L2 / H1 norms and the lumped mass.
+ * Quadrilaterals and hexahedra, 1 <= p <= 16, isoparametric.
+ *
+ * Arrays are element-major: element fields float64 [n_elem][n^ndim] with the
+ * local index lexicographic (xi0 slowest), gradients [n_elem][ndim][n^ndim].
+ * Global vectors are read and written as v[c * comp_stride + node *
+ * node_stride] (sem_points_eval's strides), c < ncomp <= 65535.  With
+ * J[c][i] = d x_c / d xi_i from x_phys and D, invJ its inverse by cofactors,
+ * detJxW = det J times the tensor of the 1-D quadrature weights
+ * (sem/discrete.py:594-597).  No per-node J / invJ is stored: every call
+ * recomputes the geometry from x_phys.  No atomics: every sum is taken in a
+ * fixed order, so two calls give the same bits. */
+typedef struct sem_volume sem_volume;
+
+/* d_x_phys: float64 [n_elem][ndim][n^ndim] exactly as sem_geom_fields writes
+ * it; d_e2n: uint32 [n_elem][n^ndim].  Both are BORROWED until
+ * sem_volume_destroy: the kernels read them at every call, the caller keeps
+ * them allocated and unchanged.  h_D [n][n] (sem_diff_matrix) and h_w [n] are
+ * read before the call returns.  The map is copied to the host once, where
+ * every id is checked before any launch and the CSR of the (element, local)
+ * entries of every node is planned, rows in ascending order
+ * (csrc/sem_volume_plan.cpp): SEM_E_INVALID for ndim not 2 or 3, p < 1,
+ * n_elem < 0 (0 is valid), n_node outside [0, 2^32], n_elem * n^ndim >= 2^31,
+ * a NULL array, an id >= n_node; SEM_E_NOTIMPL for p > 16.  One launch then
+ * computes detJ at every element node: SEM_E_DETJ, with the count in the
+ * message, when any detJ <= 0 (sem/mapping.py:117); a node kernel sums the
+ * lumped mass m[g] = sum of detJxW[e][l] over the CSR row of g, in the row's
+ * order.  The handle owns m, detJxW (one double per element node, what the
+ * integrals weigh with) and one scratch of n_elem * ndim * n^ndim doubles for
+ * the recovery.  Synchronises `stream`. */
+int sem_volume_create(sem_volume** out, int ndim, int p, int64_t n_elem, const double* d_x_phys,
+                      const uint32_t* d_e2n, int64_t n_node, const double* h_D, const double* h_w,
+                      int device, void* stream);
+void sem_volume_destroy(sem_volume* vol);
+
+/* d_m [n_node]: a copy of the lumped mass, 0 at nodes no element references.
+ * Does not synchronise. */
+int sem_volume_mass(sem_volume* vol, double* d_m, void* stream);
+
+/* d_grad[c][e][j][l] = sum_i invJ[i][j] du_c/dxi_i: FiniteElement.gradient
+ * (sem/discrete.py:680-684) of u_c[e2n[e]] for all elements, d_grad float64
+ * [ncomp][n_elem][ndim][n^ndim].  d_u holds n_node nodes per component (the
+ * caller's obligation, as in sem_points_eval; volume.VolumeSet refuses any
+ * other size).  One launch; allocates nothing and does not synchronise
+ * (graph-capturable).  SEM_E_INVALID for a NULL handle or array, ncomp
+ * outside [1, 65535], a stride < 0 / < 1. */
+int sem_volume_gradient(sem_volume* vol, int ncomp, int64_t comp_stride, int64_t node_stride,
+                        const double* d_u, double* d_grad, void* stream);
+
+/* The continuous nodal gradient, the lumped-mass L2 projection of the element
+ * gradients: d_g[c * out_comp_stride + j * out_dim_stride + node *
+ * out_node_stride] = (sum over the node's CSR row of detJxW[e][l] *
+ * grad[c][e][j][l]) / m[node], rows summed in ascending (element, local)
+ * order; 0 at nodes no element references.  Two launches per component (the
+ * element kernel into the handle's scratch, then one thread per node over its
+ * row); allocates nothing and does not synchronise.  Calls on one handle that
+ * use the scratch (this one, and the sums below when d_per_elem is NULL) must
+ * be ordered: one stream, or events. */
+int sem_volume_recover(sem_volume* vol, int ncomp, int64_t comp_stride, int64_t node_stride,
+                       const double* d_u, int64_t out_comp_stride, int64_t out_dim_stride,
+                       int64_t out_node_stride, double* d_g, void* stream);
+
+/* d_per_elem[c][e] = sum_l detJxW[e][l] u_c[e2n[e][l]] and d_total[c] = sum_e
+ * of these, for a nodal field; either output may be NULL (without d_per_elem
+ * the per-element values pass through the handle's scratch).  Fixed-order
+ * two-stage sum as sem_faces_integrate (per element, then one workgroup per
+ * component over the elements).  With no elements the totals are 0.
+ * Allocates nothing and does not synchronise. */
+int sem_volume_integrate(sem_volume* vol, int ncomp, int64_t comp_stride, int64_t node_stride,
+                         const double* d_u, double* d_per_elem, double* d_total, void* stream);
+
+/* The same for element-local values d_vals [ncomp][n_elem][n^ndim]:
+ * FiniteElement.integrate (sem/discrete.py:686-688) of every element. */
+int sem_volume_integrate_local(sem_volume* vol, int ncomp, const double* d_vals,
+                               double* d_per_elem, double* d_total, void* stream);
+
+/* With d = u - v formed at the nodes first (d_v NULL: v = 0; d_v has d_u's
+ * strides): d_per_elem[c][e][0] = sum_l detJxW d^2, [c][e][1] = sum_l detJxW
+ * |grad d|^2, the GLL-quadrature discrete L2^2 and H1-seminorm^2 (the
+ * quadrature of Lse, examples/poisson.py:166-193), and d_total[c][0..1] their
+ * fixed-order sums over the elements.  Either output may be NULL.  The
+ * gradient is never written to memory.  Allocates nothing and does not
+ * synchronise. */
+int sem_volume_norms(sem_volume* vol, int ncomp, int64_t comp_stride, int64_t node_stride,
+                     const double* d_u, const double* d_v, double* d_per_elem, double* d_total,
+                     void* stream);
+
+/* info[0] ndim, [1] p, [2] elements, [3] nodes, [4] referenced nodes,
+ * [5] longest CSR row, [6] scratch bytes.  Writes min(n_info, 7) values. */
+int sem_volume_info(sem_volume* vol, int64_t* info, int n_info);
+
+/* ------------------------------------------------------------------ */
 /* Element matrices: the dense local systems of the assembled path      */
 /* ------------------------------------------------------------------ */
 /* The dense element operators the reference builds per element in Python --

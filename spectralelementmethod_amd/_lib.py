@@ -130,6 +130,16 @@ SIGNATURES = {
     "sem_transfer_restrict": (C.c_int, [_vp, C.c_int, _i64, _i64, _vp, _i64, _i64, _vp, C.c_int,
                                         _vp]),
     "sem_transfer_info": (C.c_int, [_vp, C.POINTER(_i64), C.c_int]),
+    "sem_volume_create": (C.c_int, [C.POINTER(_vp), C.c_int, C.c_int, _i64, _vp, _vp, _i64, _dp, _dp,
+                                    C.c_int, _vp]),
+    "sem_volume_destroy": (None, [_vp]),
+    "sem_volume_mass": (C.c_int, [_vp, _vp, _vp]),
+    "sem_volume_gradient": (C.c_int, [_vp, C.c_int, _i64, _i64, _vp, _vp, _vp]),
+    "sem_volume_recover": (C.c_int, [_vp, C.c_int, _i64, _i64, _vp, _i64, _i64, _i64, _vp, _vp]),
+    "sem_volume_integrate": (C.c_int, [_vp, C.c_int, _i64, _i64, _vp, _vp, _vp, _vp]),
+    "sem_volume_integrate_local": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp]),
+    "sem_volume_norms": (C.c_int, [_vp, C.c_int, _i64, _i64, _vp, _vp, _vp, _vp, _vp]),
+    "sem_volume_info": (C.c_int, [_vp, C.POINTER(_i64), C.c_int]),
     "sem_elem_matrices": (C.c_int, [C.c_int, C.c_int, C.c_int, _i64, _vp, _dp, _dp, C.c_double,
                                     _vp, _vp, C.POINTER(C.c_int32), _i64, _i64, _vp, _vp, _vp]),
 }

@@ -610,6 +610,50 @@ class DOFManager(object):
         per mesh version like ``operator()``."""
         return self.operator().point_locator()
 
+    def volume_set(self):
+        """Device volume post-processing of this mesh (``volume.VolumeSet``),
+        cached per mesh version like ``operator()``."""
+        return self.operator().volume_set()
+
+    def _node_fields(self, u, name="u"):
+        """Host coefficients [..., n_nodes], or with several DOFs per node
+        the interleaved vector [ndof], as ``VolumeSet`` takes them."""
+        u = np.asarray(u, dtype=np.float64)
+        if self._dpn > 1 and u.shape == (self.ndof,):
+            return u, self._dpn
+        if u.ndim < 1 or u.shape[-1] != self._mesh.n_nodes:
+            raise ValueError("%s must have shape [..., n_nodes = %d]%s, got %s"
+                             % (name, self._mesh.n_nodes,
+                                " or [ndof]" if self._dpn > 1 else "", list(u.shape)))
+        return u, None
+
+    def gradient(self, u):
+        """``FiniteElement.gradient(u[fe.node_ind])`` of every element in one
+        device launch: u [..., n_nodes] -> [..., n_cells, ndim, n, n(, n)]
+        (an interleaved [ndof] vector -> [dofs_per_node, n_cells, ...])."""
+        u, dpn = self._node_fields(u)
+        return self.volume_set().gradient(u, dofs_per_node=dpn)
+
+    def integrate(self, u):
+        """The integral of nodal fields over the mesh, the sum of
+        ``FiniteElement.integrate(u[fe.node_ind])``: u [..., n_nodes] ->
+        [...], on the device."""
+        u, dpn = self._node_fields(u)
+        return self.volume_set().integrate(u, dofs_per_node=dpn)
+
+    def norm(self, u, v=None, kind="l2"):
+        """The discrete L2 norm (``kind="l2"``) or H1 seminorm (``"h1"``) of
+        u - v (of u without v) with the GLL quadrature, on the device."""
+        if kind not in ("l2", "h1"):
+            raise ValueError("kind must be 'l2' or 'h1'")
+        u, dpn = self._node_fields(u)
+        if v is not None:
+            v, dpn_v = self._node_fields(v, "v")
+            if dpn_v != dpn or v.shape != u.shape:
+                raise ValueError("u and v must have the same shape")
+        res = self.volume_set().norms(u, v, dofs_per_node=dpn)
+        return res.l2 if kind == "l2" else res.h1
+
     def interpolate(self, coeffs, x_phys):
         """Interpolate global coefficients ``coeffs[..., node]`` at physical
         points (sem/discrete.py:221-233).  One point [ndim] returns the value

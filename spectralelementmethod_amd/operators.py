@@ -226,6 +226,7 @@ class SEMOperator(object):
                                                         _lib.stream_ptr()))
         self._geom_ready = set()
         self._locator = None
+        self._volume = None
 
     @staticmethod
     def _to_map(e2n):
@@ -245,6 +246,7 @@ class SEMOperator(object):
     # ------------------------------------------------------------------
     def close(self):
         self._locator = None  # lives on while a PointSet refers to it
+        self._volume = None
         if getattr(self, "_solver", None) and self._solver[0] is not None:
             self._solver[0].close()
         self._solver = None
@@ -356,6 +358,15 @@ class SEMOperator(object):
             from .points import PointLocator
             self._locator = PointLocator(self)
         return self._locator
+
+    def volume_set(self):
+        """The ``volume.VolumeSet`` of this operator's mesh (built once):
+        gradients, the recovered nodal gradient, volume integrals, L2 / H1
+        norms and the lumped mass on the device."""
+        if self._volume is None:
+            from .volume import VolumeSet
+            self._volume = VolumeSet(self)
+        return self._volume
 
     def face_set(self, elem, face):
         """The ``faces.FaceSet`` of the given (element, face) pairs of this
