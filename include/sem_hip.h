@@ -983,6 +983,110 @@ int sem_elem_matrices(int op_kind, int ndim, int p, int64_t n_elem, const double
                       const double* d_state, const int32_t* h_local_order, int64_t elem_begin,
                       int64_t elem_count, double* d_mat, double* d_rhs, void* stream);
 
+/* ------------------------------------------------------------------ */
+/* p-multigrid: a V-cycle preconditioner of the Poisson PCG             */
+/* ------------------------------------------------------------------ */
+/* Levels p_0 > p_1 > ... > p_L on the same elements, each order a divisor of
+ * its predecessor, so that the equispaced mesh nodes of a level are a subset
+ * of the finer level's.  The reference has no counterpart (its solve is a
+ * direct one, sem/discrete.py:502-528).
+ *
+ * Host-side planning (no device, csrc/sem_mg_plan.cpp; all arrays are HOST
+ * arrays):
+ *   - sem_mg_ladder: the default ladder of order p, dividing by the smallest
+ *     prime factor down to 1 (16 8 4 2 1; 12 6 3 1; 9 3 1; 10 5 1; 7 1; 1),
+ *     into ladder[0 .. *n_levels), *n_levels <= capacity (5 always suffices).
+ *   - sem_mg_check_ladder: SEM_E_INVALID unless ladder[0 .. n_levels) is a
+ *     descending divisor chain of orders in 1..16.
+ *   - sem_mg_coarsen: e2n_coarse[e][i, j(, k)] = the node of e2n_fine[e][s i,
+ *     s j(, s k)], s = p_fine / p_coarse, with the kept fine ids compacted in
+ *     ascending order; h_keep[c] (capacity n_node_fine) is the fine id of
+ *     coarse node c, *n_node_coarse their count.  Any conforming mesh, any
+ *     numbering, no orientation logic.
+ *   - sem_mg_coarse_mask: a coarse node is fixed iff in some element that
+ *     contains it every fine node of its entity is fixed; the entity is, per
+ *     local axis, the same end of the element where the coarse local index is
+ *     an end and the open range 1 .. p_fine - 1 where it is not (the vertex
+ *     itself, an open edge, an open face or the open interior).
+ * SEM_E_INVALID for ndim not 2 or 3, orders that are no divisor pair, sizes
+ * out of range (as sem_transfer_create), a NULL array, an id >= its node
+ * count; SEM_E_NOTIMPL for p > 16 in sem_mg_ladder. */
+int sem_mg_ladder(int p, int* ladder, int capacity, int* n_levels);
+int sem_mg_check_ladder(const int* ladder, int n_levels);
+int sem_mg_coarsen(int ndim, int p_fine, int p_coarse, int64_t n_elem, const uint32_t* h_e2n_fine,
+                   int64_t n_node_fine, uint32_t* h_e2n_coarse, uint32_t* h_keep,
+                   int64_t* n_node_coarse);
+int sem_mg_coarse_mask(int ndim, int p_fine, int p_coarse, int64_t n_elem,
+                       const uint32_t* h_e2n_fine, int64_t n_node_fine, const uint8_t* h_mask_fine,
+                       const uint32_t* h_e2n_coarse, int64_t n_node_coarse,
+                       uint8_t* h_mask_coarse);
+
+/* The cycle z = M r (csrc/sem_mg.hip).  Level l: a Poisson context with one
+ * DOF per node and its geometry set, its Dirichlet mask, D = its diagonal,
+ * D^-1 := 0 on fixed DOFs.  Smoother: the degree-k Chebyshev iteration for
+ * D^-1 A on [lambda_max / ratio, lambda_max],
+ *     d = D^-1 r / theta;  then k - 1 times:  x += d, r -= A d,
+ *     d = rho' rho d + (2 rho' / delta) D^-1 r,
+ * theta = (b + a) / 2, delta = (b - a) / 2, sigma = theta / delta, rho_0 =
+ * 1 / sigma, rho' = 1 / (2 sigma - rho), and a last x += d.
+ *     level l < L:  x = smoother(b) from x = 0 (smooth_degree, smooth_ratio),
+ *                   r = (b - A x) on free DOFs, 0 on fixed ones,
+ *                   b_{l+1} = restrict(r) (sem_transfer_restrict),
+ *                   the cycle of level l + 1,
+ *                   x += prolong(x_{l+1}) on free DOFs,
+ *                   x = smoother(b) from that x (the same polynomial);
+ *     level L:      x = smoother(b) from x = 0 (coarse_degree, coarse_ratio).
+ * No inner Krylov solve or dot product: M is a fixed symmetric positive
+ * definite matrix on the free DOFs (given lambda_max[l] >= the largest
+ * eigenvalue of D^-1 A on level l's free DOFs), so plain PCG applies.  A
+ * smoothed level costs 2 smooth_degree operator actions per cycle, the
+ * coarsest coarse_degree - 1 (sem_mg_info).
+ *
+ * sem_mg_create: ctxs [n_levels] and transfers [n_levels - 1] (transfer l:
+ * "from" level l + 1 "to" level l) are BORROWED until sem_mg_destroy;
+ * d_dirichlet [n_levels] device uint8 masks (read here only);
+ * h_lambda_max [n_levels] host.  Allocates every vector the cycle and the
+ * solve use (7 per level, 1 more on level 0; rows padded to 32 doubles).
+ * SEM_E_INVALID for n_levels outside 1..16, a NULL entry, a degree < 1, a
+ * ratio <= 1, a lambda_max <= 0 or not finite, a context on another device, a
+ * transfer whose node counts differ from its two levels'; SEM_E_NOTIMPL for a
+ * context with dofs_per_node != 1.  Synchronises `stream`. */
+typedef struct sem_mg sem_mg;
+int sem_mg_create(sem_mg** out, int n_levels, sem_ctx* const* ctxs,
+                  sem_transfer* const* transfers, const uint8_t* const* d_dirichlet,
+                  const double* h_lambda_max, int smooth_degree, int coarse_degree,
+                  double smooth_ratio, double coarse_ratio, int device, void* stream);
+void sem_mg_destroy(sem_mg* mg);
+
+/* d_z = M d_r (level-0 vectors; entries of d_r on fixed DOFs are ignored, d_z
+ * is 0 there; d_z must not alias d_r).  One chain of launches on `stream`:
+ * allocates nothing and does not synchronise (graph-capturable, no parallel
+ * branches).  Calls on one handle must be ordered: they share its vectors. */
+int sem_mg_vcycle(sem_mg* mg, const double* d_r, double* d_z, void* stream);
+
+/* One cycle as sem_mg_vcycle with events between the levels' segments:
+ * h_ms [n_levels] (host) takes the milliseconds of each level (its way down
+ * plus its way up; the restriction counts to the finer level, the
+ * prolongation too).  Diagnostic: creates events and synchronises. */
+int sem_mg_profile(sem_mg* mg, const double* d_r, double* d_z, double* h_ms, void* stream);
+
+/* Solve K x = b on the free DOFs of level 0 with PCG preconditioned by the
+ * cycle; the semantics of sem_pcg_solve: d_x carries the Dirichlet values on
+ * entry, every scalar stays on the device, the r.r history is read back every
+ * check_every iterations (< 1: 1), rtol = 0 runs exactly max_iter
+ * iterations, SEM_E_INVALID when not converged or on a non-finite residual.
+ * Dot products are fixed-order two-stage sums: two solves give the same
+ * bits.  An iteration allocates nothing. */
+int sem_mg_pcg_solve(sem_mg* mg, const double* d_b, double* d_x, double rtol, int max_iter,
+                     int check_every, int* iters, double* relres, void* stream);
+
+/* info[0] levels, [1] smooth_degree, [2] coarse_degree, [3] bytes of the
+ * handle's vectors, then 5 values per level l at [4 + 5 l]: DOFs, operator
+ * actions per cycle, vector passes of this unit per cycle (both as planned),
+ * and the actions and passes the last cycle enqueued.  Writes min(n_info,
+ * 4 + 5 levels) values. */
+int sem_mg_info(sem_mg* mg, int64_t* info, int n_info);
+
 #ifdef __cplusplus
 }
 #endif

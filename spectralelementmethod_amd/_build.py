@@ -15,7 +15,8 @@ LIB_PATH = os.environ.get("SEM_LIB_PATH", os.path.join(PKG_DIR, LIB_NAME))
 SOURCES = ["sem_device.hip", "sem_dd.hip", "sem_sc.hip", "sem_basis.cpp", "sem_hex.hip",
            "sem_order.cpp", "sem_points.hip", "sem_plan.cpp", "sem_faces.hip",
            "sem_faces_plan.cpp", "sem_elmat.hip", "sem_hex_plan.cpp", "sem_transfer.hip",
-           "sem_transfer_plan.cpp", "sem_volume.hip", "sem_volume_plan.cpp"]
+           "sem_transfer_plan.cpp", "sem_volume.hip", "sem_volume_plan.cpp", "sem_mg.hip",
+           "sem_mg_plan.cpp"]
 # (lo, hi) order ranges of sem_launch.hip, balanced by compile time (the
 # unrolled column kernels grow with n)
 LAUNCH_RANGES = [(2, 5), (6, 8), (9, 9), (10, 11), (12, 13), (14, 15), (16, 16), (17, 17)]
@@ -30,7 +31,7 @@ LAUNCH_CD_RANGES = [((2, 6), ()), ((7, 7), NO_LICM), ((8, 10), ()), ((11, 13), (
 POINTS_RANGES = [(2, 9), (10, 17)]
 DEPS = SOURCES + ["sem_launch.hip", "sem_launch_cd.hip", "sem_points_launch.hip", "sem_points.h",
                   "sem_internal.h", "sem_error.h", "sem_plan.h", "sem_faces_plan.h", "sem_kernels.h", "sem_ctx.h", "sem_hex.h", "sem_hex_mfma.h", "sem_hex_plan.h", "gll_table.h",
-                  "deo_const.h", "sem_transfer_plan.h", "sem_volume_plan.h"]
+                  "deo_const.h", "sem_transfer_plan.h", "sem_volume_plan.h", "sem_mg_plan.h"]
 ARCH = os.environ.get("SEM_OFFLOAD_ARCH", "gfx950")
 
 

@@ -140,6 +140,21 @@ SIGNATURES = {
     "sem_volume_integrate_local": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp]),
     "sem_volume_norms": (C.c_int, [_vp, C.c_int, _i64, _i64, _vp, _vp, _vp, _vp, _vp]),
     "sem_volume_info": (C.c_int, [_vp, C.POINTER(_i64), C.c_int]),
+    "sem_mg_ladder": (C.c_int, [C.c_int, C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int)]),
+    "sem_mg_check_ladder": (C.c_int, [C.POINTER(C.c_int), C.c_int]),
+    "sem_mg_coarsen": (C.c_int, [C.c_int, C.c_int, C.c_int, _i64, _vp, _i64, _vp, _vp,
+                                 C.POINTER(_i64)]),
+    "sem_mg_coarse_mask": (C.c_int, [C.c_int, C.c_int, C.c_int, _i64, _vp, _i64, _vp, _vp, _i64,
+                                     _vp]),
+    "sem_mg_create": (C.c_int, [C.POINTER(_vp), C.c_int, C.POINTER(_vp), C.POINTER(_vp),
+                                C.POINTER(_vp), _dp, C.c_int, C.c_int, C.c_double, C.c_double,
+                                C.c_int, _vp]),
+    "sem_mg_destroy": (None, [_vp]),
+    "sem_mg_vcycle": (C.c_int, [_vp, _vp, _vp, _vp]),
+    "sem_mg_profile": (C.c_int, [_vp, _vp, _vp, _dp, _vp]),
+    "sem_mg_pcg_solve": (C.c_int, [_vp, _vp, _vp, C.c_double, C.c_int, C.c_int,
+                                   C.POINTER(C.c_int), C.POINTER(C.c_double), _vp]),
+    "sem_mg_info": (C.c_int, [_vp, C.POINTER(_i64), C.c_int]),
     "sem_elem_matrices": (C.c_int, [C.c_int, C.c_int, C.c_int, _i64, _vp, _dp, _dp, C.c_double,
                                     _vp, _vp, C.POINTER(C.c_int32), _i64, _i64, _vp, _vp, _vp]),
 }

@@ -960,12 +960,13 @@ class DOFManagerSC(DOFManager):
         self._solve_boundary_dofs(global_sc_system, dof_vec, on_ebc)
         self._solve_interior_dofs(local_systems, dof_vec)
 
-    def solve_poisson(self, rhs, dof_vec, on_ebc, rtol=1e-13, max_iter=20000):
+    def solve_poisson(self, rhs, dof_vec, on_ebc, rtol=1e-13, max_iter=20000, precond="jacobi"):
         """Assembled Poisson solve K u = rhs with essential BCs: the result of
         DOFManagerSC.solve (sem/discrete.py:502-528) computed matrix-free with
         Jacobi-PCG on the GPU.  ``dof_vec`` holds the EBC values (updated in
         place); ``on_ebc`` masks the exterior DOFs (reference convention) or
-        all DOFs.  Returns (dof_vec, iterations, relative residual)."""
+        all DOFs.  ``precond``: "jacobi" or "pmg" (SEMOperator.pcg_solve).
+        Returns (dof_vec, iterations, relative residual)."""
         import torch
         if self._dpn != 1:
             raise NotImplementedError("solve_poisson: scalar problems (dofs_per_node == 1)")
@@ -975,7 +976,7 @@ class DOFManagerSC(DOFManager):
         op = self.operator()
         x = torch.from_numpy(np.where(mask, dof_vec, 0.0)).to(op.device)
         b = torch.from_numpy(np.asarray(rhs, dtype=np.float64)).to(op.device)
-        x, its, rel = op.pcg_solve(b, x, mask, rtol=rtol, max_iter=max_iter)
+        x, its, rel = op.pcg_solve(b, x, mask, rtol=rtol, max_iter=max_iter, precond=precond)
         dof_vec[...] = x.cpu().numpy()
         return dof_vec, its, rel
 

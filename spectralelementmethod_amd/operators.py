@@ -247,6 +247,9 @@ class SEMOperator(object):
     def close(self):
         self._locator = None  # lives on while a PointSet refers to it
         self._volume = None
+        if getattr(self, "_pmg", None) is not None:
+            pmg, self._pmg = self._pmg, None
+            pmg.close()
         if getattr(self, "_solver", None) and self._solver[0] is not None:
             self._solver[0].close()
         self._solver = None
@@ -666,8 +669,42 @@ class SEMOperator(object):
                                         _lib.tptr(out), self._stream(stream)))
         return out
 
+    def multigrid(self, dirichlet, **kw):
+        """The ``multigrid.PMultigrid`` of this Poisson operator and Dirichlet
+        mask: a p-multigrid V-cycle over the orders p, p / (smallest prime
+        factor), ..., 1 on the same elements (keywords: ladder,
+        smooth_degree, coarse_degree, smooth_ratio, coarse_ratio).  It keeps
+        this operator alive."""
+        from .multigrid import PMultigrid
+        return PMultigrid(self, dirichlet, **kw)
+
+    def _pmg_solve(self, precond, rhs, x, dirichlet, rtol, max_iter, kind, stream, renumber,
+                   check_every):
+        """pcg_solve with the p-multigrid preconditioner: ``precond`` is "pmg"
+        (a hierarchy built here and kept for the next solve with the same
+        mask) or a PMultigrid of this operator and mask."""
+        from .multigrid import PMultigrid
+        if kind != POISSON:
+            raise NotImplementedError("pcg_solve(precond='pmg'): the Poisson operator")
+        if renumber is True or renumber == "on":
+            raise NotImplementedError("pcg_solve(precond='pmg'): the levels use the caller's "
+                                      "numbering (renumber=True is not supported)")
+        if isinstance(precond, PMultigrid):
+            precond._handle()
+            if not precond.matches(self, dirichlet):
+                raise ValueError("this PMultigrid was built for another operator or mask")
+            mg = precond
+        else:
+            mg = getattr(self, "_pmg", None)
+            if mg is None or mg._h is None or not mg.matches(self, dirichlet):
+                if mg is not None:
+                    mg.close()
+                mg = self._pmg = PMultigrid(self, dirichlet, kind=kind)
+        return mg.solve(rhs, x, rtol=rtol, max_iter=max_iter,
+                        check_every=1 if check_every is None else check_every, stream=stream)
+
     def pcg_solve(self, rhs, x, dirichlet, rtol=1e-13, max_iter=20000, kind=POISSON,
-                  stream=None, renumber="auto"):
+                  stream=None, renumber="auto", precond="jacobi", check_every=None):
         """Solve K x = rhs on the free DOFs (``dirichlet`` True => x fixed)
         with Jacobi-preconditioned CG on the device (sem_pcg_solve: every
         scalar stays on the device, convergence read every 16 iterations;
@@ -676,8 +713,24 @@ class SEMOperator(object):
         residual).  Raises ValueError when not converged.  renumber: "auto"
         solves in the kernel's traversal numbering when the caller's
         numbering reads >= 1.3x the 64-byte lines per row (row_lines; e.g.
-        the reference's RCM default), True forces it, False never."""
+        the reference's RCM default), True forces it, False never.
+        precond: "jacobi" (default), "pmg" (the p-multigrid V-cycle of
+        ``multigrid()``, built at the first such solve and kept while the
+        mask stays the same) or a ``PMultigrid`` of this operator and mask;
+        with p-multigrid the solve runs in the caller's numbering
+        (renumber="auto" resolves to off, True raises NotImplementedError)
+        and reads the residual back every ``check_every`` iterations
+        (default 1)."""
         kind = op_kind(kind)
+        if not (isinstance(precond, str) and precond == "jacobi"):
+            from .multigrid import PMultigrid
+            if not (isinstance(precond, PMultigrid) or precond == "pmg"):
+                raise ValueError("precond must be 'jacobi', 'pmg' or a PMultigrid")
+            return self._pmg_solve(precond, rhs, x, dirichlet, rtol, max_iter, kind, stream,
+                                   renumber, check_every)
+        if check_every is not None:
+            raise ValueError("check_every applies to precond='pmg' (the Jacobi solve reads the "
+                             "residual back every %d iterations)" % _lib.PCG_CHECK_EVERY)
         solver = self._solver_numbering(renumber) if kind == POISSON else None
         if solver is not None:
             op, order, inv = solver

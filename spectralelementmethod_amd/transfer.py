@@ -16,8 +16,9 @@ pair of orders in 1..16:
   order without atomics.
 
 ``SEMOperator.transfer_to(other)`` builds one from two operators on the same
-elements.  Transfers across the ranks of a decomposition and the multigrid
-cycle are out of scope.
+elements; ``multigrid.PMultigrid`` builds its V-cycle on them (DESIGN.md
+§4.15).  Transfers across the ranks of a decomposition are out of scope
+(DESIGN.md §9).
 """
 import ctypes as C
 
